@@ -9,10 +9,16 @@ A step = one pass of the hot path over the rank's batch, inputs resident in HBM:
 Weak scaling: every rank owns `--files` files (default 1440 = one day).
 
 Prints ONE JSON line on rank 0 with the roofline of the dominant kernel (the
-STFT, timed live with HIP events on the stream it runs on) and the CPU baseline
-(the numpy/scipy oracle of the reference path, 1 thread, on a bounded sample).
+STFT, timed live with HIP events on the stream it runs on).  A plain run does only
+what that headline needs: inputs, warm-up, the timed steps, the line.  --full adds
+everything else the bench measures, in the same run and the same line: the CPU
+baselines (the numpy/scipy oracle of the reference path on a bounded sample, 1
+thread and multi-process), the per-kernel breakdown (one more step with every
+kernel timed), the C4 strong-scaling pass, and the C5 and live workloads (keys
+"c5", "live").  --dump-outputs DIR writes what the last timed step computed as
+DIR/<name>.npy (see dump_c3), so that two builds can be compared output for output.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--full] [--dump-outputs DIR]
     python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N
 
 With --gpus N > 1 and no launcher environment (WORLD_SIZE unset) bench.py starts the N ranks
@@ -108,6 +114,13 @@ def parse():
                     "rendezvous a random id and rank 0 prints what every rank saw")
     ap.add_argument("--steps", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=10, help="untimed steps (the GPU clock ramps up over the first few)")
+    ap.add_argument("--full", action="store_true",
+                    help="everything beyond the headline, as the other switches select it: CPU baselines (every "
+                         "workload), and for c3 the per-kernel breakdown, the C4 strong-scaling pass and the C5 "
+                         "and live runs appended to the line")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="c3: after the timed steps, write the last step's outputs to DIR/<name>.npy (float32 / "
+                         "float64, under 64 MB; rank 0's files)")
     ap.add_argument("--files", type=int, default=1440, help="one-minute files per GPU")
     ap.add_argument("--c5-seconds", type=float, default=C5_SECONDS, help="c5: seconds of the stream per GPU "
                     "(default 3 h: 24 h over 8 GPUs)")
@@ -142,7 +155,17 @@ def parse():
                          "(Welch band powers + state machine) over a day of 4 kHz audio; c5: 192 kHz I/Q, "
                          "4096-point two-sided spectrogram, 75 %% overlap, 3 h of the 24 h stream per GPU; files: "
                          "end to end from WAV files on disk (native reader, pinned triple-buffered uploads)")
-    return ap.parse_args()
+    a = ap.parse_args()
+    if a.steps < 1 or a.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
+    if a.dump_outputs and a.workload != "c3":
+        ap.error("--dump-outputs writes the outputs of the c3 workload (the headline) only")
+    return a
+
+
+def cpu_baseline_wanted(a):
+    """the CPU baselines belong to --full (every workload); --no-cpu-baseline / --cpu-files 0 drop them there"""
+    return a.full and not a.no_cpu_baseline and a.cpu_files > 0
 
 
 def cpu_baseline(pool, nfiles):
@@ -334,7 +357,7 @@ def run_live(a, ctx, job, rank, world, rows):
     out["near_tie"] = {"files_flagged": int(lb.near_tie.sum()), "files": F,
                        "max_decision_bound_db": float(np.max(lb.decision_bounds)),
                        "min_margin_db": float(np.min(lb.min_margins))}
-    if rank == 0 and world == 1 and not a.no_cpu_baseline and a.cpu_files > 0:
+    if rank == 0 and world == 1 and cpu_baseline_wanted(a):
         nf = 6
         v, dt = cpu_baseline_live(rows, nf)
         out["cpu_baseline"] = {"value": round(v, 3), "unit": "Msamples/s", "cores": 1, "kind": "port",
@@ -543,7 +566,7 @@ def run_c5(a, ctx, job, rank, world, rows):
         out["exact_delta"] = {"kernel": "block_i8_kernel<7> + frame_kernel", "ms": dms, "bytes": xb,
                               "achieved_gbs": round(xb / (dms * 1e-3) / 1e9, 1) if dms > 0 else None,
                               "frac_of_hbm": round(xb / (dms * 1e-3) / 1e9 / HBM_PEAK_GBS, 4) if dms > 0 else None}
-    if rank == 0 and world == 1 and not a.no_cpu_baseline and a.cpu_files > 0:
+    if rank == 0 and world == 1 and cpu_baseline_wanted(a):
         from oracle import iq_oracle as Q
         mins = 10
         m = C5_FS * 60 * mins  # the first 10 minutes of the rank's stream (~8 s on one core)
@@ -696,15 +719,15 @@ def _main():
     day = 0 if a.shard_day else rank
     pool = synth_rows("real", day_seeds(day, lo, hi), FS * SECONDS, fs=FS, duration_s=SECONDS, f0=1000.0)
     spool = None  # C4 after the weak-scaling line: this rank's share of day 0, made before any GPU call
-    if not a.shard_day and (world > 1 or launch.launched()):
+    if a.full and not a.shard_day and (world > 1 or launch.launched()):
         slo, shi = shard_range(a.files, rank, world)
         spool = pool[slo:shi] if day == 0 else synth_rows("real", day_seeds(0, slo, shi), FS * SECONDS, fs=FS,
                                                           duration_s=SECONDS, f0=1000.0)
     # the C5 line's stream and the live line's day, made before any GPU call as well
-    rows5 = c5_rows(a, rank, world) if not a.no_c5 and not a.shard_day else None
-    rows_live = live_rows(rank) if not a.no_live and not a.shard_day else None
+    rows5 = c5_rows(a, rank, world) if a.full and not a.no_c5 and not a.shard_day else None
+    rows_live = live_rows(rank) if a.full and not a.no_live and not a.shard_day else None
     mp_base = None
-    if rank == 0 and world == 1 and not a.no_cpu_baseline and a.cpu_files > 0 and a.cpu_procs > 1:
+    if rank == 0 and world == 1 and cpu_baseline_wanted(a) and a.cpu_procs > 1:
         # before any GPU call: the workers are forked from this process
         mp_files = a.cpu_files * a.cpu_procs // 4
         v, dt = cpu_baseline_mp(pool, mp_files, a.cpu_procs)
@@ -714,7 +737,8 @@ def _main():
     ctx = _lib.Context(local)
     job = job_of(ctx)
     n = FS * SECONDS
-    r = run_c3(a, ctx, job, rank, world, pool, lo, hi, a.shard_day, detail=True)
+    r = run_c3(a, ctx, job, rank, world, pool, lo, hi, a.shard_day, detail=a.full,
+               dump_dir=a.dump_outputs if rank == 0 else None)
     F = hi - lo
     samples = (a.files if a.shard_day else world * F) * n
     out = {
@@ -748,9 +772,12 @@ def _main():
     }
     if "roofline" in r:
         out["roofline"] = r["roofline"]
-    out["kernel_ms_per_step"] = r["kernel_ms"]
+    if "kernel_ms" in r:
+        out["kernel_ms_per_step"] = r["kernel_ms"]
     out["near_tie"] = r["near_tie"]  # margin.py's guard over this rank's files (C3 decisions vs numpy)
-    if not a.shard_day:
+    if a.dump_outputs:
+        out["dumped"] = r.get("dumped")
+    if a.full and not a.shard_day:
         # BASELINE configs[3] (C4): the SAME 1440-file day sharded over the N ranks (strong scaling),
         # measured after the weak-scaling line so that the driver's 1/2/4/8 runs carry both curves
         if world > 1 or job is not None:
@@ -769,7 +796,7 @@ def _main():
                       "note": "N = 1: the same run as the headline line"}
         strong["ranks_seen"] = job.ranks_seen() if job is not None else 1
         out["strong_scaling"] = strong
-    if rank == 0 and world == 1 and not a.no_cpu_baseline and a.cpu_files > 0:
+    if rank == 0 and world == 1 and cpu_baseline_wanted(a):
         v, dt = cpu_baseline(pool, a.cpu_files)
         out["cpu_baseline"] = {
             "value": round(v, 2),
@@ -781,7 +808,7 @@ def _main():
         }
     if mp_base is not None:
         out["cpu_baseline_multicore"] = mp_base
-    if not a.no_c5 and not a.shard_day:
+    if rows5 is not None:
         # BASELINE configs[4] (C5) in the same run, after the C3 timed region: the driver's record
         # then carries a C5 number of its own (the full line under "c5")
         try:
@@ -810,11 +837,42 @@ def _main():
         job.close()
 
 
-def run_c3(a, ctx, job, rank, world, pool, lo, hi, one_day, detail):
+DUMP_SPEC_BYTES = 48 << 20  # --dump-outputs: the spectrogram sample's share of the 64 MB
+
+
+def dump_c3(dump_dir, bp, dets, counts, hist):
+    """--dump-outputs: what a caller of BatchPipeline receives after the last timed step, as
+    DIR/<name>.npy (float64 unless noted; every run with the same arguments has the same inputs):
+      delta, thresholds     [F][blocks]  band - noise dB per block, the threshold it was held against
+      detection_counts      [F]          detections per file
+      detections            [sum][4]     file index, start block, stop block, dB (files in order)
+      hour_counts           [24]         detections per hour of the day (all-reduced over the ranks)
+      spectrogram           float32 [S][K][T]  the whole spectrograms of a fixed seeded sample of S files
+      spectrogram_files     [S]          which files (sorted)
+    Returns {name: shape}."""
+    os.makedirs(dump_dir, exist_ok=True)
+    F = bp.nfiles
+    arrays = {"delta": bp.delta(), "thresholds": bp.thresholds(),
+              "detection_counts": counts.astype(np.float64), "hour_counts": hist.astype(np.float64)}
+    rows = [np.column_stack([np.full(len(d), i, np.float64), d["start"].astype(np.float64),
+                             d["stop"].astype(np.float64), d["db"]]) for i, d in enumerate(dets)]
+    arrays["detections"] = np.concatenate(rows) if rows else np.zeros((0, 4))
+    if bp.with_spectrogram and F:
+        ns = max(1, min(F, DUMP_SPEC_BYTES // (bp.K * bp.T * 4)))
+        files = np.sort(np.random.default_rng(0).choice(F, ns, replace=False))
+        arrays["spectrogram"] = np.stack([bp.spectrogram(int(i)) for i in files]).astype(np.float32)
+        arrays["spectrogram_files"] = files.astype(np.float64)
+    for name, arr in arrays.items():
+        np.save(os.path.join(dump_dir, name + ".npy"), np.ascontiguousarray(arr))
+    return {name: list(arr.shape) for name, arr in arrays.items()}
+
+
+def run_c3(a, ctx, job, rank, world, pool, lo, hi, one_day, detail, dump_dir=None):
     """C3 / C4: files [lo, hi) of a day on this rank (one_day: of ONE day sharded over the ranks,
     else day `rank`); warm-up, then a.steps timed steps.  Returns the max-over-ranks time, the
-    detections, the all-reduced hour total and (detail) the roofline and kernel breakdown.  The
-    pipeline is freed before returning."""
+    detections, the all-reduced hour total, the roofline and (detail: one more step) the kernel
+    breakdown; dump_dir: the last timed step's outputs are written there (dump_c3).  The pipeline
+    is freed before returning."""
     from meteorgpu import _lib
     from meteorgpu.batch import BatchPipeline
     n = FS * SECONDS
@@ -865,7 +923,7 @@ def run_c3(a, ctx, job, rank, world, pool, lo, hi, one_day, detail):
     import warnings
     with warnings.catch_warnings():  # the near-tie guard's verdict is reported in the line instead
         warnings.simplefilter("ignore")
-        _, counts, status, margins = bp.detections()
+        dets, counts, status, margins = bp.detections()
     assert (status == 0).all(), "detector status"
     near = {"files_flagged": int(bp.near_tie.sum()), "files": F,
             "max_decision_bound_db": float(np.max(bp.decision_bounds)) if F else 0.0,
@@ -880,6 +938,8 @@ def run_c3(a, ctx, job, rank, world, pool, lo, hi, one_day, detail):
     stft_ms, stft_launches = ctx.timing_get(_lib.K_STFT)
     res = {"elapsed": elapsed, "detections": total_dets, "hour_total": int(hist.sum()), "T": bp.T, "K": bp.K,
            "near_tie": near}
+    if dump_dir:
+        res["dumped"] = dump_c3(dump_dir, bp, dets, counts, hist)
     if not a.no_spectrogram and stft_launches:
         avg_s = stft_ms / stft_launches / 1e3
         alg_bytes = F * (n * 2 + bp.K * bp.T * 4)  # samples read once + spectrogram written once

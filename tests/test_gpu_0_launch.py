@@ -31,8 +31,8 @@ def _bench(*args, timeout=240):
 
 
 def test_spawn_c3():
-    """the default line: C3 (weak), the C4 strong-scaling pass over the same ranks, C5 and live appended"""
-    d = _bench("--files", "16", "--c5-seconds", "60")
+    """the --full line: C3 (weak), the C4 strong-scaling pass over the same ranks, C5 and live appended"""
+    d = _bench("--full", "--files", "16", "--c5-seconds", "60")
     assert d["scaling"] == "weak" and d["config"]["files_per_gpu"] == 16 and d["roofline"]["frac"] > 0
     s = d["strong_scaling"]
     assert s["scaling"] == "strong" and s["files_total"] == 16 and s["ranks_seen"] == 1 and s["value"] > 0

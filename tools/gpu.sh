@@ -6,6 +6,8 @@
 #   tools/gpu.sh test   NAME [pytest args]      pytest -m gpu over the args (default: the whole suite)
 #   tools/gpu.sh smoke                          __graft_entry__.smoke()
 #   tools/gpu.sh bench  NAME [bench.py args]    one bench line → gpurun_out/NAME.json, summary printed
+#                                               (pass --full for the kernel breakdown, the CPU baselines
+#                                               and the c5 / live legs the summary prints)
 #   tools/gpu.sh c5     NAME REPS [bench args]  REPS exact-mode C5 benches (certified headline)
 #   tools/gpu.sh trace  NAME [bench.py args]    rocprofv3 --kernel-trace --stats of a bench run +
 #                                               tools/trace_gaps.py step timeline

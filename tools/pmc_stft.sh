@@ -7,7 +7,7 @@ ROOT=${GRAFT_REPO_ROOT:-$(cd "$(dirname "$0")/.." && pwd)}
 OUT=$ROOT/gpurun_out/pmc/$TAG
 mkdir -p "$OUT"
 cd /tmp && export TMPDIR=/tmp
-ARGS=${*:-"--files 1440 --steps 2 --warmup 1 --no-cpu-baseline --no-c5 --no-live"}
+ARGS=${*:-"--full --files 1440 --steps 2 --warmup 1 --no-cpu-baseline --no-c5 --no-live"}
 i=0
 # PMC_GROUPS="grp1;grp2": other counter groups (one pass each)
 IFS=';' read -r -a GROUPS_ <<< "${PMC_GROUPS:-}"
