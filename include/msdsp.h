@@ -498,6 +498,99 @@ int msd_live_detect_dev(msd_ctx *ctx, const double *band_db, const int64_t *nblo
 int msd_live_detect(msd_ctx *ctx, const double *band_db /* [3][nb] */, int64_t nb, const msd_live_cfg *cfg,
                     msd_meteor *out, int64_t cap, int64_t *count, double *thresholds, double *over);
 
+/* ------------------------------------- a8 + a9 resumable: the live session
+ * The reference station grabs 30 s of audio every 30 s around the clock
+ * (meteor_detect_class/prime_detection.py:32, :148-163) and its phase-2 detector
+ * (processor.py:391-507) is stateful across them.  A session holds nstreams independent
+ * audio streams (receivers / frequencies of one station) and takes each stream's audio, or
+ * its band-dB rows, in pushes of any length, empty ones included.  For any split of a stream
+ * into pushes, the per-push outputs concatenated -- band-dB rows, over-noise values,
+ * thresholds used, meteors and their order -- are bit-identical to msd_welch_bands followed
+ * by msd_live_detect on the concatenated input.  Times are global: block b of a stream
+ * starts at (b*block_size)/fs whichever push brought it.
+ *
+ * Kept on the device per stream between pushes: the detector state (msd_live_stream_state),
+ * the samples that did not fill a block (< block_size), and the over-noise values a later
+ * block can still read: everything from block keep = min(blocks - W, trig while Tracking) on
+ * (W = avg_win_blocks; W = 0, the reference's over[-0:], keeps everything).  That tail lives
+ * in hist_blocks + max_push_blocks doubles per stream.  When, after a push, more than
+ * hist_blocks values would have to stay (W = 0 on a long stream; a tracking run that never
+ * ends, e.g. a continuous carrier), the stream's status becomes 4 (history overflow): the
+ * outputs of that push are still valid, and from then on the stream is frozen -- later pushes
+ * leave its state alone, emit nothing for it (0 blocks, 0 meteors) and report 4 again --
+ * until it is reset.  The other streams are unaffected.
+ *
+ * Per-push status[f]: 0; 3 = more meteors closed in this push than cap (only cap kept);
+ * 4 = history overflow.  counts[f] = meteors closed in THIS push, at out[f*cap ..].
+ *
+ * The _dev pushes enqueue on the context's stream and never synchronise with the host, at
+ * any push length (one wave per stream scans the push's blocks in order from the carried
+ * state; there are no fixed-point rounds and no convergence flag to read).  The one exception
+ * is a scratch buffer of the context growing, which can only happen on a session's first
+ * pushes.  The host forms, the state getter and the history getter return after the results
+ * are on the host. */
+typedef struct msd_live_session msd_live_session;
+typedef struct { /* one stream's carried state (aggregates.py:4-24 + the session's counters) */
+    int32_t state;     /* 0 StateInitialization, 1 StateDetection, 2 StateTracking */
+    int32_t status;    /* 0, or 4 = history overflow (frozen until reset) */
+    int64_t blocks;    /* blocks consumed */
+    int64_t trig;      /* Tracking: the global index of the block that triggered it */
+    double lock;       /* locked_threshold */
+    double until;      /* use_locked_threshold_until_secs */
+    double t_start;    /* time_start_detection */
+    int64_t meteors;   /* meteors closed since creation / reset */
+    int64_t retained;  /* over-noise values kept: those of blocks [blocks - retained, blocks) */
+    int64_t remainder; /* samples carried (< block_size) */
+} msd_live_stream_state;
+/* welch (may be NULL: the session then takes rows only) with its window as for
+ * msd_welch_plan_create; it must have the three bands and cfg's block_size.  dtype: the
+ * MSD_U8..MSD_F64 format of every sample push (ignored without welch).  max_push_blocks >= 1:
+ * the most blocks one push may bring per stream; hist_blocks >= cfg->avg_win_blocks.
+ * Device memory: 8 * (hist_blocks + 3 * max_push_blocks) bytes per stream for the detector,
+ * plus (max_push_blocks + 2) blocks of samples and 24 * max_push_blocks bytes with welch. */
+int msd_live_session_create(msd_ctx *ctx, const msd_live_cfg *cfg, const msd_welch_cfg *welch, const double *window,
+                            int64_t nstreams, int64_t max_push_blocks, int64_t hist_blocks, int dtype,
+                            msd_live_session **out);
+void msd_live_session_destroy(msd_live_session *s);
+/* rows: band_db[(f*3 + j)*ld + b] and device nblocks[f] as for msd_live_detect_dev; stream f
+ * takes min(nblocks[f], max_blocks) rows, max_blocks <= min(ld, max_push_blocks).
+ * thresholds / over (each may be NULL): the new blocks' values at [f*ld + b]; counts, status
+ * (may be NULL): per stream, above.  No host synchronisation. */
+int msd_live_session_push_rows_dev(msd_live_session *s, const double *band_db, const int64_t *nblocks,
+                                   int64_t max_blocks, int64_t ld, msd_meteor *out, int64_t cap, int64_t *counts,
+                                   double *thresholds, double *over, int32_t *status);
+/* samples: stream f's new samples are x[off[f] .. off[f] + min(len[f], max_len)) (device off /
+ * len as for msd_welch_bands_dev; max_len <= max_push_blocks * block_size, x may be NULL when
+ * it is 0).  They follow the stream's carried remainder; the whole blocks go through the
+ * Welch launch of msd_welch_bands_dev (int16: the int8 path, as there) and the detector, the
+ * rest is carried.  new_blocks[f] (may be NULL): blocks completed by this push; band_db,
+ * thresholds, over (each may be NULL): their rows / values, laid out as above with
+ * ld >= (block_size - 1 + max_len) / block_size.  No host synchronisation. */
+int msd_live_session_push_samples_dev(msd_live_session *s, const void *x, const int64_t *off, const int64_t *len,
+                                      int64_t max_len, msd_meteor *out, int64_t cap, int64_t *counts,
+                                      int64_t *new_blocks, double *band_db, double *thresholds, double *over,
+                                      int64_t ld, int32_t *status);
+/* host buffers, one stream (the others get an empty push): band_db [3][nb]; thresholds / over
+ * (may be NULL) [nb]; *count may exceed cap (MSD_ERR_CAPACITY, cap meteors kept); *status (may
+ * be NULL) as above.  Synchronous. */
+int msd_live_session_push_rows(msd_live_session *s, int64_t stream, const double *band_db, int64_t nb,
+                               msd_meteor *out, int64_t cap, int64_t *count, double *thresholds, double *over,
+                               int32_t *status);
+/* host buffers, one stream: n samples of the session's dtype; band_db (may be NULL) [3][ld],
+ * thresholds / over (may be NULL) [ld], ld >= (block_size - 1 + n) / block_size. */
+int msd_live_session_push_samples(msd_live_session *s, int64_t stream, const void *x, int64_t n, msd_meteor *out,
+                                  int64_t cap, int64_t *count, int64_t *new_blocks, double *band_db,
+                                  double *thresholds, double *over, int64_t ld, int32_t *status);
+/* the states of streams [first, first + n) to the host.  Synchronous. */
+int msd_live_session_state(msd_live_session *s, int64_t first, int64_t n, msd_live_stream_state *out);
+/* one stream's retained over-noise values (those of blocks [blocks - retained, blocks), e.g.
+ * StateTracking's history over[trig + 1 ..]) to the host: *n of them, at most cap copied.
+ * Synchronous. */
+int msd_live_session_history(msd_live_session *s, int64_t stream, double *out, int64_t cap, int64_t *n);
+/* stream >= 0: that stream, -1: all, back to Init at block 0 with empty history and remainder
+ * and status 0.  Enqueued on the context's stream. */
+int msd_live_session_reset(msd_live_session *s, int64_t stream);
+
 /* ------------------------------------------- a1 / §8(f)1: WAV ingest and uploads
  * scipy.io.wavfile.read semantics for the reference's files (dsp/src/main.py:249; the rules in
  * csrc/wav_parse.h): RIFF little-endian; the sample container is nBlockAlign / nChannels; PCM

@@ -19,6 +19,9 @@
 // live_seg_{init,scan,link,emit}_kernel: the state machine in 256-block time segments, one wave
 // each over the whole GPU (ballots), rounds of scan + link to a fixed point over their entry states,
 // then one emitting pass.
+// live_session_*_kernel: the same detector fed in pushes (msdsp.h, live session): the state, the
+// over-noise tail and the samples short of a block stay on the device; one wave per stream scans a
+// push's blocks in order from the carried state (no rounds, no host synchronisation).
 #include <cmath>
 
 #include "msd_internal.h"
@@ -238,8 +241,8 @@ __device__ __forceinline__ void hist_stats(const double *ov, int64_t b, int64_t 
 // reaches them, so they hold no flat instruction (np_reduce.h, tests/test_build_check.py).
 
 // Detection → Tracking (processor.py:462-472): locked_threshold = thr + 0 * history_std
-__device__ __noinline__ LiveScan live_trigger(LiveScan sc, const double *ov, int64_t i, double t, double t0,
-                                              int64_t W) {
+__device__ __forceinline__ LiveScan live_trigger_body(LiveScan sc, const double *ov, int64_t i, double t, double t0,
+                                                      int64_t W) {
     const int64_t h0 = W > 0 ? (i - W > 0 ? i - W : 0) : 0;
     double hm = NAN, hs = NAN;
     if (i - h0 > 0) hist_stats(ov, h0, i - h0, hm, hs, nullptr, nullptr);
@@ -249,11 +252,15 @@ __device__ __noinline__ LiveScan live_trigger(LiveScan sc, const double *ov, int
     sc.state = 2;
     return sc;
 }
+__device__ __noinline__ LiveScan live_trigger(LiveScan sc, const double *ov, int64_t i, double t, double t0,
+                                              int64_t W) {
+    return live_trigger_body(sc, ov, i, t, t0, W);
+}
 
 // Tracking ends (processor.py:474-504): history = over[trig+1 .. i]
-__device__ __noinline__ LiveScan live_close(LiveScan sc, const double *ov, int64_t i, double t0, double min_db_mean,
-                                            double min_dur_sec, double wait_sec, msd_meteor *out, int64_t cap,
-                                            bool writer) {
+__device__ __forceinline__ LiveScan live_close_body(LiveScan sc, const double *ov, int64_t i, double t0,
+                                                    double min_db_mean, double min_dur_sec, double wait_sec,
+                                                    msd_meteor *out, int64_t cap, bool writer) {
     const double dur = t0 - sc.t_start;
     double hm, hs, mn, mx;
     hist_stats(ov, sc.trig + 1, i - sc.trig, hm, hs, &mn, &mx);
@@ -277,6 +284,11 @@ __device__ __noinline__ LiveScan live_close(LiveScan sc, const double *ov, int64
     sc.state = 1;
     sc.until = t0 + wait_sec;
     return sc;
+}
+__device__ __noinline__ LiveScan live_close(LiveScan sc, const double *ov, int64_t i, double t0, double min_db_mean,
+                                            double min_dur_sec, double wait_sec, msd_meteor *out, int64_t cap,
+                                            bool writer) {
+    return live_close_body(sc, ov, i, t0, min_db_mean, min_dur_sec, wait_sec, out, cap, writer);
 }
 
 // processor.py:391: block_db_2_ms = block_db_ms - np.mean([n1, n2])
@@ -353,7 +365,9 @@ __device__ __forceinline__ double live_tblk(const msd_live_cfg &C, int64_t i) {
     return (double)(i * (int64_t)C.block_size) / C.fs;
 }
 
-// one wave's pass over blocks [a, b) of one file from sc; emit: write the thresholds used and the meteors
+// one wave's pass over blocks [a, b) of one file from sc; emit: write the thresholds used and the meteors.
+// INL: the event handlers inlined (the live session's kernel, which may not call: tests/test_build_check.py)
+template <bool INL>
 __device__ __forceinline__ void live_scan(LiveScan &sc, int64_t a, int64_t b, bool emit, const double *ov, double *th,
                                           const msd_live_cfg &C, msd_meteor *outf, int64_t cap, int lane) {
     int64_t k = a;
@@ -388,10 +402,13 @@ __device__ __forceinline__ void live_scan(LiveScan &sc, int64_t a, int64_t b, bo
             sc.lock = -1.0;
             sc.until = -1.0;
         } else if (sc.state == 1) {
-            sc = live_trigger(sc, ov, e, te, t0e, C.avg_win_blocks);
+            sc = INL ? live_trigger_body(sc, ov, e, te, t0e, C.avg_win_blocks)
+                     : live_trigger(sc, ov, e, te, t0e, C.avg_win_blocks);
         } else {
-            sc = live_close(sc, ov, e, t0e, C.min_db_mean, C.min_dur_sec, C.after_tracking_wait_sec, outf, cap,
-                            emit && lane == 0);
+            sc = INL ? live_close_body(sc, ov, e, t0e, C.min_db_mean, C.min_dur_sec, C.after_tracking_wait_sec, outf,
+                                       cap, emit && lane == 0)
+                     : live_close(sc, ov, e, t0e, C.min_db_mean, C.min_dur_sec, C.after_tracking_wait_sec, outf, cap,
+                                  emit && lane == 0);
         }
         k = e + 1;
     }
@@ -439,7 +456,7 @@ __global__ __launch_bounds__(256) void live_seg_scan_kernel(const int64_t *__res
     const int64_t a = s * LV_SEGLEN, b = a + LV_SEGLEN < nb ? a + LV_SEGLEN : nb;
     LiveScan sc = S.in[i];
     sc.cnt = 0;
-    live_scan(sc, a, b, false, over + f * A.L.ld, thr + f * A.L.ld, A.L.cfg, nullptr, 0, lane);
+    live_scan<false>(sc, a, b, false, over + f * A.L.ld, thr + f * A.L.ld, A.L.cfg, nullptr, 0, lane);
     if (lane == 0) {
         S.out[i] = sc;
         S.cnt[i] = sc.cnt;
@@ -485,7 +502,7 @@ __global__ __launch_bounds__(256) void live_seg_emit_kernel(const int64_t *__res
     for (int o = 32; o > 0; o >>= 1) off += __shfl_xor(off, o, 64);
     LiveScan sc = S.in[i];
     sc.cnt = off;
-    live_scan(sc, a, b, true, over + f * A.L.ld, thr + f * A.L.ld, A.L.cfg, out + f * A.L.cap, A.L.cap, lane);
+    live_scan<false>(sc, a, b, true, over + f * A.L.ld, thr + f * A.L.ld, A.L.cfg, out + f * A.L.cap, A.L.cap, lane);
     if (lane == 0 && b == nb) {
         counts[f] = sc.cnt;
         if (status) status[f] = sc.cnt > A.L.cap ? 3 : 0;
@@ -602,10 +619,266 @@ int launch_live(msd_ctx *ctx, const double *band_db, const int64_t *nblocks, int
     return MSD_OK;
 }
 
+// ---------------------------------------------------------------- live session (msdsp.h)
+// Per stream f the device keeps an msd_live_stream_state and hist[f][0 .. retained): the over-noise
+// values of the global blocks [base, blocks), base = blocks - retained.  A push appends its n new
+// values behind them, computes the fresh thresholds with the look-back running into the tail, scans
+// the new blocks from the carried state (one wave per stream, live_scan over global block indices)
+// and shifts the tail down to the new keep.  The history and threshold pointers handed to live_scan
+// are displaced so that the global block index addresses them (hist - base, thr - blocks); every
+// index the scan and its event handlers form lies in [keep, blocks + n).
+struct LsArgs {
+    msd_live_cfg cfg;
+    int64_t nstreams, max_blocks;  // max_blocks: this push's bound on the new blocks per stream
+    int64_t H, hcap;               // hist_blocks, hcap = H + max_push_blocks doubles per stream
+    int64_t cap;
+};
+
+__device__ __forceinline__ int64_t ls_new_blocks(const int64_t *nblocks, int64_t f, const LsArgs &A) {
+    const int64_t n = nblocks[f];
+    return n < 0 ? 0 : (n < A.max_blocks ? n : A.max_blocks);
+}
+
+// processor.py:391 for the push's new blocks, appended behind the retained tail
+__global__ __launch_bounds__(WL_THREADS) void live_session_over_kernel(const double *__restrict__ band_db, int64_t ld,
+                                                                        const int64_t *__restrict__ nblocks, LsArgs A,
+                                                                        const msd_live_stream_state *__restrict__ st,
+                                                                        double *__restrict__ hist,
+                                                                        double *__restrict__ over, int64_t ld_over) {
+    const int64_t f = blockIdx.y;
+    const int64_t i = (int64_t)blockIdx.x * WL_THREADS + threadIdx.x;
+    if (st[f].status == 4 || i >= ls_new_blocks(nblocks, f, A)) return;
+    const double *sig = band_db + (f * 3 + 0) * ld;
+    const double *n1 = band_db + (f * 3 + 1) * ld;
+    const double *n2 = band_db + (f * 3 + 2) * ld;
+    const double m = (-0.0 + n1[i] + n2[i]) / 2.0;
+    const double v = sig[i] - m;
+    hist[f * A.hcap + st[f].retained + i] = v;  // retained <= H, i < P
+    over[f * ld_over + i] = v;
+}
+
+// processor.py:392-402 for the new blocks: the look-back runs into the tail (local index l of global
+// block blocks + i; the tail starts at or before global block - W, or at block 0)
+__global__ __launch_bounds__(WL_THREADS) void live_session_history_kernel(const int64_t *__restrict__ nblocks, LsArgs A,
+                                                                           const msd_live_stream_state *__restrict__ st,
+                                                                           const double *__restrict__ hist,
+                                                                           double *__restrict__ thr, int64_t ld_thr) {
+    const int64_t f = blockIdx.y;
+    const int64_t i = (int64_t)blockIdx.x * WL_THREADS + threadIdx.x;
+    if (st[f].status == 4 || i >= ls_new_blocks(nblocks, f, A)) return;
+    const int64_t W = A.cfg.avg_win_blocks;
+    const int64_t l = st[f].retained + i;
+    const int64_t h0 = W > 0 ? (l - W > 0 ? l - W : 0) : 0;
+    const int64_t hn = l - h0;
+    double mean = NAN, sd = NAN;
+    if (hn > 0) np_mean_std(hist + f * A.hcap, h0, hn, mean, sd);
+    thr[f * ld_thr + i] = mean + A.cfg.k_std * sd;
+}
+
+// one wave per stream: the state machine over the new blocks from the carried state (thresholds used
+// and meteors written), the exit state, and the tail shifted down to the new keep.  The shift is in
+// place: this wave alone touches the stream's history, it moves 64 values per step downwards by
+// shift >= 1, and step k's stores [64 k, 64 k + 64) lie below every later load (>= shift + 64 (k + 1)),
+// so no load can see a moved value.
+__global__ __launch_bounds__(256) void live_session_scan_kernel(const int64_t *__restrict__ nblocks, LsArgs A,
+                                                                msd_live_stream_state *__restrict__ st,
+                                                                double *__restrict__ hist, double *__restrict__ thr,
+                                                                int64_t ld_thr, msd_meteor *__restrict__ out,
+                                                                int64_t *__restrict__ counts,
+                                                                int32_t *__restrict__ status,
+                                                                int64_t *__restrict__ new_blocks,
+                                                                const int64_t *__restrict__ new_rem) {
+    const int64_t f = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (f >= A.nstreams) return;  // wave-uniform
+    const int lane = threadIdx.x & 63;
+    const msd_live_stream_state S = st[f];
+    if (S.status == 4) {  // frozen: nothing consumed, nothing emitted
+        if (lane == 0) {
+            if (counts) counts[f] = 0;
+            if (status) status[f] = 4;
+            if (new_blocks) new_blocks[f] = 0;
+        }
+        return;
+    }
+    const int64_t n = ls_new_blocks(nblocks, f, A);
+    const int64_t base = S.blocks - S.retained, nb2 = S.blocks + n;
+    double *hf = hist + f * A.hcap;
+    LiveScan sc;
+    sc.state = S.state;
+    sc.lock = S.lock;
+    sc.until = S.until;
+    sc.t_start = S.t_start;
+    sc.trig = S.trig;
+    sc.cnt = 0;  // meteors closed in this push
+    live_scan<true>(sc, S.blocks, nb2, true, hf - base, thr + f * ld_thr - S.blocks, A.cfg, out + f * A.cap, A.cap,
+                    lane);
+    const int64_t W = A.cfg.avg_win_blocks;
+    int64_t keep = W > 0 ? nb2 - W : 0;
+    if (sc.state == 2 && sc.trig < keep) keep = sc.trig;
+    if (keep < base) keep = base;
+    const int64_t shift = keep - base, kept = nb2 - keep;
+    if (shift > 0) {
+        for (int64_t j0 = 0; j0 < kept; j0 += 64) {
+            const int64_t j = j0 + lane;
+            if (j < kept) {
+                const double v = hf[shift + j];
+                hf[j] = v;
+            }
+        }
+    }
+    if (lane == 0) {
+        const bool overflow = kept > A.H;  // the next push's P values would no longer fit behind it
+        msd_live_stream_state E;
+        E.state = sc.state;
+        E.status = overflow ? 4 : 0;
+        E.blocks = nb2;
+        E.trig = sc.trig;
+        E.lock = sc.lock;
+        E.until = sc.until;
+        E.t_start = sc.t_start;
+        E.meteors = S.meteors + sc.cnt;
+        E.retained = kept;
+        E.remainder = new_rem ? new_rem[f] : S.remainder;
+        st[f] = E;
+        if (counts) counts[f] = sc.cnt;
+        if (status) status[f] = overflow ? 4 : (sc.cnt > A.cap ? 3 : 0);
+        if (new_blocks) new_blocks[f] = n;
+    }
+}
+
+// [carried remainder | new samples] of every stream into the staging buffer, and the Welch launch's
+// offsets / lengths (whole blocks only), block counts and new remainder counts into meta [4][nstreams]
+template <typename E>
+__global__ __launch_bounds__(256) void live_session_gather_kernel(const E *__restrict__ x,
+                                                                  const int64_t *__restrict__ off,
+                                                                  const int64_t *__restrict__ len, int64_t max_len,
+                                                                  int64_t nstreams, int64_t B,
+                                                                  const msd_live_stream_state *__restrict__ st,
+                                                                  const E *__restrict__ rem, E *__restrict__ stage,
+                                                                  int64_t stride, int64_t *__restrict__ meta) {
+    const int64_t f = blockIdx.y;
+    const int64_t j = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    const bool frozen = st[f].status == 4;
+    const int64_t r = st[f].remainder;  // < B
+    int64_t L = len[f];
+    L = L < 0 ? 0 : (L < max_len ? L : max_len);
+    const int64_t total = r + L, nb = total / B;  // total < (P + 1) B <= stride
+    if (j == 0) {
+        meta[f] = f * stride;
+        meta[nstreams + f] = frozen ? 0 : nb * B;
+        meta[2 * nstreams + f] = frozen ? 0 : nb;
+        meta[3 * nstreams + f] = frozen ? r : total - nb * B;
+    }
+    if (frozen || j >= total) return;
+    stage[f * stride + j] = j < r ? rem[f * B + j] : x[off[f] + (j - r)];
+}
+
+// the samples behind the last whole block become the stream's remainder
+template <typename E>
+__global__ __launch_bounds__(256) void live_session_carry_kernel(int64_t nstreams, int64_t B,
+                                                                 const msd_live_stream_state *__restrict__ st,
+                                                                 const E *__restrict__ stage, int64_t stride,
+                                                                 const int64_t *__restrict__ meta,
+                                                                 E *__restrict__ rem) {
+    const int64_t f = blockIdx.y;
+    const int64_t j = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (st[f].status == 4 || j >= meta[3 * nstreams + f]) return;
+    rem[f * B + j] = stage[f * stride + meta[nstreams + f] + j];
+}
+
+__global__ __launch_bounds__(256) void live_session_reset_kernel(msd_live_stream_state *__restrict__ st, int64_t first,
+                                                                 int64_t n) {
+    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (i >= n) return;
+    msd_live_stream_state E;
+    E.state = 0;
+    E.status = 0;
+    E.blocks = 0;
+    E.trig = 0;
+    E.lock = -1.0;
+    E.until = -1.0;
+    E.t_start = 0.0;
+    E.meteors = 0;
+    E.retained = 0;
+    E.remainder = 0;
+    st[first + i] = E;
+}
+
 }  // namespace
 }  // namespace msd
 
 using namespace msd;
+
+struct msd_live_session {
+    msd_ctx *ctx = nullptr;
+    msd_live_cfg cfg{};
+    msd_welch_plan *plan = nullptr;  // null: rows only
+    int dtype = 0;
+    int64_t F = 0, P = 0, H = 0, stride = 0;  // stride: samples per stream of the staging buffer
+    msd_live_stream_state *d_state = nullptr;
+    double *d_hist = nullptr;   // [F][H + P]
+    double *d_thr = nullptr;    // [F][P]      thresholds / over / band rows of a push whose caller
+    double *d_over = nullptr;   // [F][P]      passes no buffer of its own
+    double *d_band = nullptr;   // [F][3][P]
+    void *d_stage = nullptr;    // [F][stride] samples
+    void *d_rem = nullptr;      // [F][block_size] samples
+    int64_t *d_meta = nullptr;  // [4][F] gather's Welch offsets / lengths, block counts, remainders
+    int64_t *d_aux = nullptr;   // [4][F] the host forms' nblocks / off / len, counts, new blocks
+    int32_t *d_status = nullptr;
+};
+
+namespace {
+
+int ls_reset(msd_live_session *s, int64_t first, int64_t n) {
+    hipLaunchKernelGGL(live_session_reset_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s->ctx->stream,
+                       s->d_state, first, n);
+    MSD_HIP(hipGetLastError());
+    return MSD_OK;
+}
+
+// over, fresh thresholds, scan + exit state + compaction for the push's rows (ld: their stride)
+int ls_detect(msd_live_session *s, const double *band_db, const int64_t *nblocks, int64_t max_blocks, int64_t ld,
+              msd_meteor *out, int64_t cap, int64_t *counts, double *thr, int64_t ld_thr, double *over,
+              int64_t ld_over, int32_t *status, int64_t *new_blocks, const int64_t *new_rem) {
+    LsArgs A{};
+    A.cfg = s->cfg;
+    A.nstreams = s->F;
+    A.max_blocks = max_blocks;
+    A.H = s->H;
+    A.hcap = s->H + s->P;
+    A.cap = cap;
+    hipStream_t st = s->ctx->stream;
+    KernelTimer timer(s->ctx, K_LIVE);
+    if (max_blocks > 0) {
+        const dim3 grid((unsigned)((max_blocks + WL_THREADS - 1) / WL_THREADS), (unsigned)s->F);
+        hipLaunchKernelGGL(live_session_over_kernel, grid, dim3(WL_THREADS), 0, st, band_db, ld, nblocks, A, s->d_state,
+                           s->d_hist, over, ld_over);
+        hipLaunchKernelGGL(live_session_history_kernel, grid, dim3(WL_THREADS), 0, st, nblocks, A, s->d_state,
+                           s->d_hist, thr, ld_thr);
+    }
+    hipLaunchKernelGGL(live_session_scan_kernel, dim3((unsigned)((s->F + 3) / 4)), dim3(256), 0, st, nblocks, A,
+                       s->d_state, s->d_hist, thr, ld_thr, out, counts, status, new_blocks, new_rem);
+    MSD_HIP(hipGetLastError());
+    return MSD_OK;
+}
+
+template <typename E>
+int ls_gather(msd_live_session *s, const void *x, const int64_t *off, const int64_t *len, int64_t max_len) {
+    const int64_t B = s->cfg.block_size;
+    hipStream_t st = s->ctx->stream;
+    const dim3 grid((unsigned)((B + max_len + 255) / 256), (unsigned)s->F);
+    KernelTimer timer(s->ctx, K_WELCH);  // the Welch launch's ingest
+    hipLaunchKernelGGL(live_session_gather_kernel<E>, grid, dim3(256), 0, st, static_cast<const E *>(x), off, len,
+                       max_len, s->F, B, s->d_state, static_cast<const E *>(s->d_rem), static_cast<E *>(s->d_stage),
+                       s->stride, s->d_meta);
+    hipLaunchKernelGGL(live_session_carry_kernel<E>, dim3((unsigned)((B + 255) / 256), (unsigned)s->F), dim3(256), 0,
+                       st, s->F, B, s->d_state, static_cast<const E *>(s->d_stage), s->stride, s->d_meta,
+                       static_cast<E *>(s->d_rem));
+    MSD_HIP(hipGetLastError());
+    return MSD_OK;
+}
+
+}  // namespace
 
 extern "C" {
 
@@ -791,6 +1064,241 @@ int msd_live_detect(msd_ctx *ctx, const double *band_db, int64_t nb, const msd_l
     MSD_HIP(hipStreamSynchronize(ctx->stream));
     if (cnt > cap) return fail(MSD_ERR_CAPACITY, "live: more meteors than capacity");
     return MSD_OK;
+}
+
+int msd_live_session_create(msd_ctx *ctx, const msd_live_cfg *cfg, const msd_welch_cfg *welch, const double *window,
+                            int64_t nstreams, int64_t max_push_blocks, int64_t hist_blocks, int dtype,
+                            msd_live_session **out) {
+    if (!out || !cfg) return fail(MSD_ERR_INVALID, "msd_live_session_create: null cfg or out");
+    *out = nullptr;
+    int rc = check_live_cfg(cfg);
+    if (rc) return rc;
+    if (nstreams < 1 || nstreams > 0x7fffffLL) return fail(MSD_ERR_INVALID, "msd_live_session_create: nstreams < 1");
+    if (max_push_blocks < 1) return fail(MSD_ERR_INVALID, "msd_live_session_create: max_push_blocks < 1");
+    if (hist_blocks < cfg->avg_win_blocks)
+        return fail(MSD_ERR_INVALID, "msd_live_session_create: hist_blocks < avg_win_blocks");
+    if (welch) {
+        if (!window) return fail(MSD_ERR_INVALID, "msd_live_session_create: null window");
+        if (welch->block_size != cfg->block_size || welch->nbands != 3)
+            return fail(MSD_ERR_INVALID, "msd_live_session_create: welch needs cfg's block_size and 3 bands");
+        if (!dtype_size(dtype)) return fail(MSD_ERR_INVALID, "msd_live_session_create: unknown dtype");
+    }
+    if (!ctx) return fail(MSD_ERR_INVALID, "msd_live_session_create: null ctx");
+    DeviceGuard g(ctx->device);
+    auto *s = new msd_live_session();
+    s->ctx = ctx;
+    s->cfg = *cfg;
+    s->dtype = dtype;
+    s->F = nstreams;
+    s->P = max_push_blocks;
+    s->H = hist_blocks;
+    const size_t F = (size_t)nstreams, P = (size_t)max_push_blocks, H = (size_t)hist_blocks;
+    hipError_t e = hipMalloc(&s->d_state, sizeof(msd_live_stream_state) * F);
+    if (e == hipSuccess) e = hipMalloc(&s->d_hist, sizeof(double) * F * (H + P));
+    if (e == hipSuccess) e = hipMalloc(&s->d_thr, sizeof(double) * F * P);
+    if (e == hipSuccess) e = hipMalloc(&s->d_over, sizeof(double) * F * P);
+    if (e == hipSuccess) e = hipMalloc(&s->d_meta, sizeof(int64_t) * 4 * F);
+    if (e == hipSuccess) e = hipMalloc(&s->d_aux, sizeof(int64_t) * 4 * F);
+    if (e == hipSuccess) e = hipMalloc(&s->d_status, sizeof(int32_t) * F);
+    if (e == hipSuccess && welch) {
+        const size_t es = dtype_size(dtype), B = (size_t)cfg->block_size;
+        s->stride = (int64_t)(((P + 1) * B + 63) / 64 * 64);  // every stream's blocks aligned as a file's are
+        e = hipMalloc(&s->d_band, sizeof(double) * F * 3 * P);
+        if (e == hipSuccess) e = hipMalloc(&s->d_stage, es * F * (size_t)s->stride + 256);
+        if (e == hipSuccess) e = hipMalloc(&s->d_rem, es * F * B);
+    }
+    if (e != hipSuccess) {
+        msd_live_session_destroy(s);
+        return hip_fail(e, "msd_live_session_create");
+    }
+    if (welch && (rc = msd_welch_plan_create(ctx, welch, window, &s->plan))) {
+        msd_live_session_destroy(s);
+        return rc;
+    }
+    if ((rc = ls_reset(s, 0, s->F))) {
+        msd_live_session_destroy(s);
+        return rc;
+    }
+    *out = s;
+    return MSD_OK;
+}
+
+void msd_live_session_destroy(msd_live_session *s) {
+    if (!s) return;
+    DeviceGuard g(s->ctx->device);
+    (void)hipStreamSynchronize(s->ctx->stream);
+    if (s->plan) msd_welch_plan_destroy(s->plan);
+    for (void *p : {(void *)s->d_state, (void *)s->d_hist, (void *)s->d_thr, (void *)s->d_over, (void *)s->d_band,
+                    s->d_stage, s->d_rem, (void *)s->d_meta, (void *)s->d_aux, (void *)s->d_status})
+        if (p) (void)hipFree(p);
+    delete s;
+}
+
+int msd_live_session_push_rows_dev(msd_live_session *s, const double *band_db, const int64_t *nblocks,
+                                   int64_t max_blocks, int64_t ld, msd_meteor *out, int64_t cap, int64_t *counts,
+                                   double *thresholds, double *over, int32_t *status) {
+    if (!s || !nblocks || (max_blocks > 0 && !band_db) || (!out && cap))
+        return fail(MSD_ERR_INVALID, "msd_live_session_push_rows_dev: null");
+    if (max_blocks < 0 || max_blocks > s->P || max_blocks > ld || cap < 0)
+        return fail(MSD_ERR_INVALID, "msd_live_session_push_rows_dev: need 0 <= max_blocks <= min(ld, max_push_blocks)");
+    DeviceGuard g(s->ctx->device);
+    return ls_detect(s, band_db, nblocks, max_blocks, ld, out, cap, counts, thresholds ? thresholds : s->d_thr,
+                     thresholds ? ld : s->P, over ? over : s->d_over, over ? ld : s->P, status, nullptr, nullptr);
+}
+
+int msd_live_session_push_samples_dev(msd_live_session *s, const void *x, const int64_t *off, const int64_t *len,
+                                      int64_t max_len, msd_meteor *out, int64_t cap, int64_t *counts,
+                                      int64_t *new_blocks, double *band_db, double *thresholds, double *over,
+                                      int64_t ld, int32_t *status) {
+    if (!s || !off || !len || (max_len > 0 && !x) || (!out && cap))
+        return fail(MSD_ERR_INVALID, "msd_live_session_push_samples_dev: null");
+    if (!s->plan) return fail(MSD_ERR_INVALID, "msd_live_session_push_samples_dev: the session takes rows only");
+    const int64_t B = s->cfg.block_size;
+    if (max_len < 0 || max_len > s->P * B || cap < 0)
+        return fail(MSD_ERR_INVALID, "msd_live_session_push_samples_dev: need 0 <= max_len <= max_push_blocks * block_size");
+    const int64_t max_blocks = (B - 1 + max_len) / B;  // <= P
+    if ((band_db || thresholds || over) && ld < max_blocks)
+        return fail(MSD_ERR_INVALID, "msd_live_session_push_samples_dev: ld < (block_size - 1 + max_len) / block_size");
+    DeviceGuard g(s->ctx->device);
+    int rc;
+    switch (dtype_size(s->dtype)) {
+        case 1: rc = ls_gather<uint8_t>(s, x, off, len, max_len); break;
+        case 2: rc = ls_gather<uint16_t>(s, x, off, len, max_len); break;
+        case 4: rc = ls_gather<uint32_t>(s, x, off, len, max_len); break;
+        default: rc = ls_gather<uint64_t>(s, x, off, len, max_len); break;
+    }
+    if (rc) return rc;
+    double *band = band_db ? band_db : s->d_band;
+    const int64_t ld_band = band_db ? ld : s->P;
+    const int64_t F = s->F;
+    if ((rc = launch_welch(s->plan, s->d_stage, s->dtype, s->d_meta, s->d_meta + F, F, max_blocks, band, ld_band,
+                           nullptr)))
+        return rc;
+    return ls_detect(s, band, s->d_meta + 2 * F, max_blocks, ld_band, out, cap, counts,
+                     thresholds ? thresholds : s->d_thr, thresholds ? ld : s->P, over ? over : s->d_over,
+                     over ? ld : s->P, status, new_blocks, s->d_meta + 3 * F);
+}
+
+// the host forms' epilogue: stream f's count, status, meteors and the new blocks' values to the host
+static int ls_fetch(msd_live_session *s, int64_t f, const msd_meteor *dmet, int64_t cap,
+                    msd_meteor *out, int64_t *count, int64_t *new_blocks, double *band_db, double *thresholds,
+                    double *over, int64_t ld, int32_t *status) {
+    hipStream_t st = s->ctx->stream;
+    const int64_t F = s->F;
+    int64_t cnt = 0, nb = 0;
+    int32_t stat = 0;
+    MSD_HIP(hipMemcpyAsync(&cnt, s->d_aux + 2 * F + f, sizeof(cnt), hipMemcpyDeviceToHost, st));
+    MSD_HIP(hipMemcpyAsync(&stat, s->d_status + f, sizeof(stat), hipMemcpyDeviceToHost, st));
+    MSD_HIP(hipMemcpyAsync(&nb, s->d_aux + 3 * F + f, sizeof(nb), hipMemcpyDeviceToHost, st));
+    MSD_HIP(hipStreamSynchronize(st));
+    *count = cnt;
+    if (new_blocks) *new_blocks = nb;
+    if (status) *status = stat;
+    const int64_t ncopy = cnt < cap ? cnt : cap;
+    if (ncopy > 0) MSD_HIP(hipMemcpyAsync(out, dmet + f * cap, sizeof(msd_meteor) * ncopy, hipMemcpyDeviceToHost, st));
+    if (nb > 0) {
+        const size_t bytes = sizeof(double) * (size_t)nb;
+        if (band_db)
+            for (int j = 0; j < 3; ++j)
+                MSD_HIP(hipMemcpyAsync(band_db + j * ld, s->d_band + (f * 3 + j) * s->P, bytes, hipMemcpyDeviceToHost, st));
+        if (thresholds) MSD_HIP(hipMemcpyAsync(thresholds, s->d_thr + f * s->P, bytes, hipMemcpyDeviceToHost, st));
+        if (over) MSD_HIP(hipMemcpyAsync(over, s->d_over + f * s->P, bytes, hipMemcpyDeviceToHost, st));
+    }
+    MSD_HIP(hipStreamSynchronize(st));
+    if (cnt > cap) return fail(MSD_ERR_CAPACITY, "live session: more meteors than capacity");
+    return MSD_OK;
+}
+
+int msd_live_session_push_rows(msd_live_session *s, int64_t stream, const double *band_db, int64_t nb,
+                               msd_meteor *out, int64_t cap, int64_t *count, double *thresholds, double *over,
+                               int32_t *status) {
+    if (!s || (!band_db && nb) || (!out && cap) || !count) return fail(MSD_ERR_INVALID, "msd_live_session_push_rows: null");
+    if (stream < 0 || stream >= s->F || nb < 0 || nb > s->P || cap < 0)
+        return fail(MSD_ERR_INVALID, "msd_live_session_push_rows: stream or nb (<= max_push_blocks) out of range");
+    msd_ctx *ctx = s->ctx;
+    DeviceGuard g(ctx->device);
+    const int64_t F = s->F, ld = nb > 0 ? nb : 1, dcap = cap > 0 ? cap : 1;
+    // scratch: the rows of every stream slot [F][3][ld] (only `stream`'s are read) | meteors [F][dcap]
+    const size_t b_rows = sizeof(double) * 3 * (size_t)ld * (size_t)F;
+    void *sp;
+    int rc;
+    if ((rc = ctx_scratch(ctx, 3, b_rows + sizeof(msd_meteor) * (size_t)dcap * (size_t)F, &sp))) return rc;
+    double *drows = static_cast<double *>(sp);
+    msd_meteor *dmet = reinterpret_cast<msd_meteor *>(static_cast<char *>(sp) + b_rows);
+    std::vector<int64_t> nbs((size_t)F, 0);
+    nbs[(size_t)stream] = nb;
+    hipStream_t st = ctx->stream;
+    if (nb) MSD_HIP(hipMemcpyAsync(drows + stream * 3 * ld, band_db, sizeof(double) * 3 * nb, hipMemcpyHostToDevice, st));
+    MSD_HIP(hipMemcpyAsync(s->d_aux, nbs.data(), sizeof(int64_t) * F, hipMemcpyHostToDevice, st));
+    MSD_HIP(hipStreamSynchronize(st));  // nbs leaves scope below
+    if ((rc = ls_detect(s, drows, s->d_aux, nb, ld, dmet, dcap, s->d_aux + 2 * F, s->d_thr, s->P, s->d_over, s->P,
+                        s->d_status, s->d_aux + 3 * F, nullptr)))
+        return rc;
+    return ls_fetch(s, stream, dmet, dcap, out, count, nullptr, nullptr, thresholds, over, 0, status);
+}
+
+int msd_live_session_push_samples(msd_live_session *s, int64_t stream, const void *x, int64_t n, msd_meteor *out,
+                                  int64_t cap, int64_t *count, int64_t *new_blocks, double *band_db,
+                                  double *thresholds, double *over, int64_t ld, int32_t *status) {
+    if (!s || (!x && n) || (!out && cap) || !count) return fail(MSD_ERR_INVALID, "msd_live_session_push_samples: null");
+    if (!s->plan) return fail(MSD_ERR_INVALID, "msd_live_session_push_samples: the session takes rows only");
+    const int64_t B = s->cfg.block_size;
+    if (stream < 0 || stream >= s->F || n < 0 || n > s->P * B || cap < 0)
+        return fail(MSD_ERR_INVALID, "msd_live_session_push_samples: stream or n (<= max_push_blocks * block_size) out of range");
+    if ((band_db || thresholds || over) && ld < (B - 1 + n) / B)
+        return fail(MSD_ERR_INVALID, "msd_live_session_push_samples: ld < (block_size - 1 + n) / block_size");
+    msd_ctx *ctx = s->ctx;
+    DeviceGuard g(ctx->device);
+    const int64_t F = s->F, dcap = cap > 0 ? cap : 1;
+    const size_t es = dtype_size(s->dtype);
+    void *dx, *dm;
+    int rc;
+    if ((rc = ctx_scratch(ctx, 0, ((size_t)n * es + 255) / 256 * 256, &dx))) return rc;
+    if ((rc = ctx_scratch(ctx, 3, sizeof(msd_meteor) * (size_t)dcap * (size_t)F, &dm))) return rc;
+    msd_meteor *dmet = static_cast<msd_meteor *>(dm);
+    std::vector<int64_t> meta((size_t)(2 * F), 0);  // off | len
+    meta[(size_t)(F + stream)] = n;
+    hipStream_t st = ctx->stream;
+    if (n) MSD_HIP(hipMemcpyAsync(dx, x, (size_t)n * es, hipMemcpyHostToDevice, st));
+    MSD_HIP(hipMemcpyAsync(s->d_aux, meta.data(), sizeof(int64_t) * 2 * F, hipMemcpyHostToDevice, st));
+    MSD_HIP(hipStreamSynchronize(st));  // meta leaves scope below
+    if ((rc = msd_live_session_push_samples_dev(s, dx, s->d_aux, s->d_aux + F, n, dmet, dcap, s->d_aux + 2 * F,
+                                                s->d_aux + 3 * F, nullptr, nullptr, nullptr, 0, s->d_status)))
+        return rc;
+    return ls_fetch(s, stream, dmet, dcap, out, count, new_blocks, band_db, thresholds, over, ld, status);
+}
+
+int msd_live_session_state(msd_live_session *s, int64_t first, int64_t n, msd_live_stream_state *out) {
+    if (!s || (!out && n)) return fail(MSD_ERR_INVALID, "msd_live_session_state: null");
+    if (first < 0 || n < 0 || first + n > s->F) return fail(MSD_ERR_INVALID, "msd_live_session_state: streams out of range");
+    if (!n) return MSD_OK;
+    DeviceGuard g(s->ctx->device);
+    MSD_HIP(hipMemcpyAsync(out, s->d_state + first, sizeof(msd_live_stream_state) * (size_t)n, hipMemcpyDeviceToHost,
+                           s->ctx->stream));
+    MSD_HIP(hipStreamSynchronize(s->ctx->stream));
+    return MSD_OK;
+}
+
+int msd_live_session_history(msd_live_session *s, int64_t stream, double *out, int64_t cap, int64_t *n) {
+    if (!s || !n || (!out && cap)) return fail(MSD_ERR_INVALID, "msd_live_session_history: null");
+    if (stream < 0 || stream >= s->F || cap < 0) return fail(MSD_ERR_INVALID, "msd_live_session_history: stream out of range");
+    msd_live_stream_state S;
+    if (int rc = msd_live_session_state(s, stream, 1, &S)) return rc;
+    *n = S.retained;
+    const int64_t m = S.retained < cap ? S.retained : cap;
+    if (m <= 0) return MSD_OK;
+    DeviceGuard g(s->ctx->device);
+    MSD_HIP(hipMemcpyAsync(out, s->d_hist + stream * (s->H + s->P), sizeof(double) * (size_t)m, hipMemcpyDeviceToHost,
+                           s->ctx->stream));
+    MSD_HIP(hipStreamSynchronize(s->ctx->stream));
+    return MSD_OK;
+}
+
+int msd_live_session_reset(msd_live_session *s, int64_t stream) {
+    if (!s) return fail(MSD_ERR_INVALID, "msd_live_session_reset: null");
+    if (stream < -1 || stream >= s->F) return fail(MSD_ERR_INVALID, "msd_live_session_reset: stream out of range");
+    DeviceGuard g(s->ctx->device);
+    return stream < 0 ? ls_reset(s, 0, s->F) : ls_reset(s, stream, 1);
 }
 
 }  // extern "C"

@@ -5,12 +5,14 @@ Public surface (mirrors the reference's dsp/src/main.py):
     get_detections, get_detections_adaptive, spectrogram, write_csv,
     write_audacity_labels, count_per_hour
 Batch / multi-GPU: meteorgpu.batch.BatchPipeline.
+Live detector fed in chunks as the audio arrives: LiveSession (meteorgpu.live).
 All numerics run in libmsdsp.so (HIP, gfx950); there is no CPU fallback.
 """
 from .dsp import (OutputDetection, ProcResult, block_powers, count_per_hour, get_detections,
                   get_detections_adaptive, proc_wav_file, process_samples, spectrogram, write_audacity_labels,
                   write_csv)
+from .live import LiveSession
 
-__all__ = ["OutputDetection", "ProcResult", "block_powers", "count_per_hour", "get_detections",
+__all__ = ["LiveSession", "OutputDetection", "ProcResult", "block_powers", "count_per_hour", "get_detections",
            "get_detections_adaptive", "proc_wav_file", "process_samples", "spectrogram", "write_audacity_labels",
            "write_csv"]

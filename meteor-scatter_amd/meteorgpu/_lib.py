@@ -117,6 +117,24 @@ class MsdLiveCfg(C.Structure):
     ]
 
 
+class MsdLiveStreamState(C.Structure):
+    """msd_live_stream_state: one stream's carried detector state (include/msdsp.h, live session)"""
+    _fields_ = [
+        ("state", C.c_int32),
+        ("status", C.c_int32),
+        ("blocks", C.c_int64),
+        ("trig", C.c_int64),
+        ("lock", C.c_double),
+        ("until", C.c_double),
+        ("t_start", C.c_double),
+        ("meteors", C.c_int64),
+        ("retained", C.c_int64),
+        ("remainder", C.c_int64),
+    ]
+
+
+LIVE_STATUS_CAPACITY, LIVE_STATUS_OVERFLOW = 3, 4
+
 METEOR_DTYPE = np.dtype([("start_block", np.int64), ("stop_block", np.int64), ("time_start", np.float64),
                          ("time_stop", np.float64), ("duration", np.float64), ("db_min", np.float64),
                          ("db_max", np.float64), ("db_mean", np.float64), ("db_std", np.float64)])
@@ -205,6 +223,22 @@ _SIGS = [
      [_P, _P, _P, C.c_int64, C.c_int64, C.POINTER(MsdLiveCfg), _P, C.c_int64, _P, _P, _P, _P]),
     ("msd_live_detect", C.c_int,
      [_P, _P, C.c_int64, C.POINTER(MsdLiveCfg), _P, C.c_int64, C.POINTER(C.c_int64), _P, _P]),
+    ("msd_live_session_create", C.c_int,
+     [_P, C.POINTER(MsdLiveCfg), C.POINTER(MsdWelchCfg), _P, C.c_int64, C.c_int64, C.c_int64, C.c_int,
+      C.POINTER(_P)]),
+    ("msd_live_session_destroy", None, [_P]),
+    ("msd_live_session_push_rows_dev", C.c_int,
+     [_P, _P, _P, C.c_int64, C.c_int64, _P, C.c_int64, _P, _P, _P, _P]),
+    ("msd_live_session_push_samples_dev", C.c_int,
+     [_P, _P, _P, _P, C.c_int64, _P, C.c_int64, _P, _P, _P, _P, _P, C.c_int64, _P]),
+    ("msd_live_session_push_rows", C.c_int,
+     [_P, C.c_int64, _P, C.c_int64, _P, C.c_int64, C.POINTER(C.c_int64), _P, _P, C.POINTER(C.c_int32)]),
+    ("msd_live_session_push_samples", C.c_int,
+     [_P, C.c_int64, _P, C.c_int64, _P, C.c_int64, C.POINTER(C.c_int64), C.POINTER(C.c_int64), _P, _P, _P,
+      C.c_int64, C.POINTER(C.c_int32)]),
+    ("msd_live_session_state", C.c_int, [_P, C.c_int64, C.c_int64, _P]),
+    ("msd_live_session_history", C.c_int, [_P, C.c_int64, _P, C.c_int64, C.POINTER(C.c_int64)]),
+    ("msd_live_session_reset", C.c_int, [_P, C.c_int64]),
     ("msd_wav_probe", C.c_int, [C.c_char_p, C.POINTER(MsdWavInfo)]),
     ("msd_wav_read", C.c_int, [C.c_char_p, C.c_int32, C.c_int64, C.c_int64, _P, C.c_int64, C.POINTER(MsdWavInfo)]),
     ("msd_host_alloc", C.c_int, [_P, C.c_size_t, C.POINTER(_P)]),

@@ -11,7 +11,8 @@ full rows of the initialisation blocks that set its colour range).  The live UI 
 it raises ``NotImplementedError``.
 
 Lower-level pieces: ``welch_band_db`` (band dB rows of one signal), ``live_detect`` (the
-state machine over band dB rows), ``LiveBatch`` (many recordings resident in HBM).
+state machine over band dB rows), ``LiveBatch`` (many recordings resident in HBM),
+``LiveSession`` (the detector fed in chunks as the audio arrives, state kept on the GPU).
 """
 from __future__ import annotations
 
@@ -501,6 +502,344 @@ class LiveBatch:
                 f"{idx.size} file(s) {idx.tolist()[:10]} have a decision within the over-noise error bound of "
                 f"their threshold: a meteor boundary may differ from the scipy reference"), stacklevel=2)
         return self.near_tie
+
+
+# ------------------------------------------------------------------ live session (resumable)
+class LiveSession:
+    """The live detector fed as the audio arrives (include/msdsp.h, live session): ``nstreams``
+    independent streams, each pushed in chunks of any length -- the reference station's 30 s grabs
+    (meteor_detect_class/prime_detection.py:148-163), single blocks, empty pushes.  The state
+    machine, the over-noise history and the samples that do not fill a block stay on the GPU
+    between pushes, so the concatenated per-push results are bit-identical to ``welch_band_db``
+    + ``live_detect`` over the concatenated stream: no 8 s blind spell per grab, no lock dropped
+    and no meteor cut at a grab boundary.  Times are those of the stream (block b starts at
+    b * block_size / fs).
+
+    ``dtype`` / ``sample_scale``: the samples' format and the factor to soundfile's float64, as
+    ``_device_samples`` gives them (uint8 audio is pushed as uint8 and shifted here, scale 1/128).
+    ``max_push_sec``: the longest chunk one device push takes (longer ``push`` calls are split).
+    ``hist_sec``: the over-noise history the GPU can keep per stream, 8 bytes per block per
+    stream; it has to cover ``avg_win_sec`` and the longest tracking run.  None: ``avg_win_sec``
+    + 15 minutes (36 KB per stream at 0.2 s blocks).  A stream that outgrows it (a continuous
+    carrier; ``avg_win_sec`` so short that the window is 0 blocks = all history) gets status 4
+    and is frozen until ``reset``; the other streams carry on.
+
+    Per stream (lists indexed by stream): ``blocks``, ``status`` (0, 3 = more meteors in one push
+    than the buffer holds, 4 = history overflow), ``state`` (a ``StateInitialization`` /
+    ``StateDetection`` / ``StateTracking``), and the cumulative near-tie guard ``near_tie``,
+    ``min_margin``, ``decision_bound`` (margin.py, live part; sample pushes only), which at the end
+    of a stream equal ``wav_file_process``'s.  ``last_band_db`` / ``last_thresholds`` /
+    ``last_over``: the new blocks of the last push, per stream."""
+
+    HIST_ALLOWANCE_SEC = 900.0
+
+    def __init__(self, fs, config_detection: ConfigDetection, nstreams: int = 1, dtype=np.int16,
+                 sample_scale: float = 1.0 / 32768.0, max_push_sec: float = 60.0, hist_sec: float | None = None,
+                 device: int = 0, warn: bool = True):
+        self.fs, self.cfg, self.F = fs, config_detection, int(nstreams)
+        self.in_dtype = np.dtype(dtype)
+        self.dev_dtype = np.dtype(np.int16) if self.in_dtype == np.uint8 else self.in_dtype
+        self.sample_scale = float(sample_scale)
+        self.warn = warn
+        self.ctx = context(device)
+        self.wcfg, self.win = welch_cfg(fs, config_detection, self.sample_scale)
+        self.lcfg = live_cfg(fs, config_detection)
+        self.B = int(self.lcfg.block_size)
+        self.W = int(self.lcfg.avg_win_blocks)
+        bsec = config_detection.proc_block_sec
+        self.P = max(1, int(np.ceil(max_push_sec / bsec - 1e-9)))
+        if hist_sec is None:
+            hist_sec = config_detection.avg_win_sec + self.HIST_ALLOWANCE_SEC
+        self.H = max(self.W, int(np.ceil(hist_sec / bsec - 1e-9)))
+        self.cap = self.P // 2 + 2  # a meteor takes a trigger and a closing block
+        lib, C = self.ctx.lib, _lib.C
+        h = C.c_void_p()
+        _lib.check(lib.msd_live_session_create(self.ctx.h, C.byref(self.lcfg), C.byref(self.wcfg), _lib.ptr(self.win),
+                                               self.F, self.P, self.H, _lib.dtype_code(self.dev_dtype), C.byref(h)))
+        self.h = h
+        F, P = self.F, self.P
+        a = self.ctx.alloc
+        self.d_x = a(F * P * self.B * self.dev_dtype.itemsize)
+        self.d_off, self.d_len, self.d_counts, self.d_newb = a(F * 8), a(F * 8), a(F * 8), a(F * 8)
+        self.d_status = a(F * 4)
+        self.d_met = a(F * self.cap * _lib.METEOR_DTYPE.itemsize)
+        self.d_band, self.d_thr, self.d_over = a(F * 3 * P * 8), a(F * P * 8), a(F * P * 8)
+        self._first = self._first_decision_block()
+        self._init_host()
+
+    # ---- host-side bookkeeping (the near-tie guard's running values, the remainder's copy)
+    def _init_host(self, stream=None):
+        idx = range(self.F) if stream is None else [stream]
+        if stream is None:
+            self.status = [0] * self.F
+            self.near_tie = [False] * self.F
+            self.min_margin = [float("inf")] * self.F
+            self.decision_bound = [0.0] * self.F
+            self._rem = [None] * self.F
+            self._blocks = [0] * self.F
+            self._big = [0.0] * self.F
+            self._emax = [0.0] * self.F
+            self._guarded = [False] * self.F
+            self.last_band_db = [np.zeros((3, 0))] * self.F
+            self.last_thresholds = [np.zeros(0)] * self.F
+            self.last_over = [np.zeros(0)] * self.F
+        for f in idx:
+            self.status[f], self.near_tie[f], self.min_margin[f], self.decision_bound[f] = 0, False, float("inf"), 0.0
+            self._rem[f] = np.zeros(0, self.dev_dtype)
+            self._blocks[f], self._big[f], self._emax[f], self._guarded[f] = 0, 0.0, 0.0, False
+            self.last_band_db[f], self.last_thresholds[f], self.last_over[f] = np.zeros((3, 0)), np.zeros(0), np.zeros(0)
+
+    def _first_decision_block(self) -> int:
+        """the first block that can leave Init (processor.py:452-455), as ``_first_decision_block``"""
+        wait = self.cfg.init_detection_wait_sec
+        b = max(0, int(np.ceil(wait * self.fs / self.B)) - 2)
+        while (b * self.B) / self.fs < wait:
+            b += 1
+        return b
+
+    def _samples(self, x) -> np.ndarray:
+        if x is None:
+            return np.zeros(0, self.dev_dtype)
+        x = np.ascontiguousarray(x)
+        if x.ndim != 1:
+            raise ValueError("a stream's samples must be 1-D")
+        if x.size and x.dtype != self.in_dtype:
+            raise TypeError(f"the session takes {self.in_dtype} samples, got {x.dtype}")
+        if self.in_dtype == np.uint8:
+            return x.astype(np.int16) - 128  # as _device_samples
+        return x.astype(self.dev_dtype, copy=False)
+
+    def _meteors(self, rows):
+        return [DetectedMeteor(float(r["time_start"]), float(r["time_stop"]), float(r["duration"]),
+                               float(r["db_min"]), float(r["db_max"]), float(r["db_mean"]), float(r["db_std"]))
+                for r in rows]
+
+    def _collect(self, found, bands, thrs, overs, with_band: bool, newb=None):
+        """download one device push's results and add them to the per-stream accumulators (newb: the
+        new blocks per stream where the caller knows them, else the device's count)"""
+        F, P = self.F, self.P
+        counts, stat = np.empty(F, np.int64), np.empty(F, np.int32)
+        self.d_counts.download(counts)
+        if newb is None:
+            newb = np.empty(F, np.int64)
+            self.d_newb.download(newb)
+        self.d_status.download(stat)
+        thr, over = np.empty((F, P)), np.empty((F, P))
+        self.d_thr.download(thr)
+        self.d_over.download(over)
+        band = np.empty((F, 3, P))
+        if with_band:
+            self.d_band.download(band)
+        rows = np.empty((F, self.cap), _lib.METEOR_DTYPE)
+        if (counts > 0).any():
+            self.d_met.download(rows)
+        for f in range(F):
+            n = int(newb[f])
+            self.status[f] = int(stat[f])
+            if int(stat[f]) == _lib.LIVE_STATUS_CAPACITY:
+                raise _lib.MsdError(_lib.MSD_ERR_CAPACITY, f"live session: stream {f} closed {int(counts[f])} meteors "
+                                                            f"in one push, the buffer holds {self.cap}")
+            found[f].extend(self._meteors(rows[f, : min(int(counts[f]), self.cap)]))
+            thrs[f].append(thr[f, :n].copy())
+            overs[f].append(over[f, :n].copy())
+            if with_band:
+                bands[f].append(band[f, :, :n].copy())
+        return newb
+
+    def _guard(self, f: int, chunk: np.ndarray, bdb: np.ndarray, thr: np.ndarray, over: np.ndarray):
+        """the near-tie guard over a push's new blocks of stream f (``chunk``: their samples, the
+        carried remainder first): running min margin and maxima, the bound from the maxima so far"""
+        n = bdb.shape[1]
+        if n:
+            c = self.wcfg
+            bands = [(int(c.band_lo[j]), int(c.band_hi[j])) for j in range(3)]
+            span = margin.block_span(chunk, self.B, self.sample_scale)[:n]
+            absmax = margin.block_absmax(chunk, self.B, self.sample_scale)[:n] if self.dev_dtype == np.int16 else None
+            err = margin.live_over_error(bdb, block_size=self.B, nperseg=int(c.nperseg), noverlap=int(c.noverlap),
+                                         nfft=int(c.nfft), window=self.win, span=span, bands=bands,
+                                         scale=float(c.scale), absmax=absmax)
+            b0 = self._blocks[f]
+            sel = slice(max(0, self._first - b0), None)
+            o, t = over[sel], thr[sel]
+            ok = np.isfinite(o) & np.isfinite(t)
+            if ok.any():
+                self.min_margin[f] = min(self.min_margin[f], float(np.min(np.abs(o[ok] - t[ok]))))
+            fin = over[np.isfinite(over)]
+            if fin.size:
+                self._big[f] = max(self._big[f], float(np.max(np.abs(fin))))
+            self._emax[f] = float(np.maximum(self._emax[f], np.max(err)))
+            self._guarded[f] = True
+        if self._guarded[f]:
+            k = self.cfg.threshold_std_factor
+            self.decision_bound[f] = (2.0 + abs(float(k))) * self._emax[f] * (1.0 + 1e-6) \
+                + 8.0 * (self.W + 8) * margin.U * self._big[f]
+            m = self.min_margin[f]
+            near = bool(np.isfinite(m)) and m <= self.decision_bound[f]
+            if near and not self.near_tie[f] and self.warn:
+                import warnings
+                warnings.warn(margin.NearTieWarning(
+                    f"stream {f}: decision margin {m:.3e} dB is within the over-noise error bound "
+                    f"{self.decision_bound[f]:.3e} dB: a meteor boundary may differ from the scipy reference"),
+                    stacklevel=4)
+            self.near_tie[f] = self.near_tie[f] or near
+
+    def _finish(self, single, found, bands, thrs, overs):
+        for f in range(self.F):
+            self.last_thresholds[f] = np.concatenate(thrs[f]) if thrs[f] else np.zeros(0)
+            self.last_over[f] = np.concatenate(overs[f]) if overs[f] else np.zeros(0)
+            self.last_band_db[f] = np.concatenate(bands[f], axis=1) if bands[f] else np.zeros((3, 0))
+        return found[0] if single else found
+
+    def _streams(self, x, ndim1):
+        """(single, list of per-stream inputs): one array for a one-stream session, or a sequence"""
+        single = isinstance(x, np.ndarray) and x.ndim == ndim1
+        xs = [x] if single else list(x)
+        if len(xs) != self.F:
+            raise ValueError(f"the session has {self.F} stream(s), got {len(xs)} input(s)")
+        return single, xs
+
+    # ---- pushes
+    def push(self, x):
+        """New samples: a 1-D array (one-stream session) or a sequence with one entry per stream
+        (arrays of any lengths, empty or None for nothing new).  Returns the ``DetectedMeteor``s
+        closed by this push: a list, or one list per stream."""
+        lib, C = self.ctx.lib, _lib.C
+        single, xs = self._streams(x, 1)
+        xs = [self._samples(v) for v in xs]
+        F, B, P = self.F, self.B, self.P
+        found, bands, thrs, overs = ([[] for _ in range(F)] for _ in range(4))
+        step = P * B
+        pos = 0
+        longest = max(len(v) for v in xs)
+        while True:
+            parts = [v[pos: pos + step] for v in xs]
+            lens = np.array([len(p) for p in parts], np.int64)
+            offs = np.concatenate([[0], np.cumsum(lens)[:-1]]).astype(np.int64)
+            if lens.sum():
+                self.d_x.upload(np.concatenate(parts))
+            self.d_off.upload(offs)
+            self.d_len.upload(lens)
+            _lib.check(lib.msd_live_session_push_samples_dev(
+                self.h, self.d_x.ptr, self.d_off.ptr, self.d_len.ptr, int(lens.max()), self.d_met.ptr, self.cap,
+                self.d_counts.ptr, self.d_newb.ptr, self.d_band.ptr, self.d_thr.ptr, self.d_over.ptr, P,
+                self.d_status.ptr))
+            frozen = [st == _lib.LIVE_STATUS_OVERFLOW for st in self.status]
+            newb = self._collect(found, bands, thrs, overs, True)
+            for f in range(F):
+                if frozen[f]:
+                    continue  # its remainder stays as it is
+                chunk = np.concatenate([self._rem[f], parts[f]])
+                n = int(newb[f])
+                self._guard(f, chunk, bands[f][-1], thrs[f][-1], overs[f][-1])
+                self._rem[f] = chunk[n * B:]
+                self._blocks[f] += n
+            pos += step
+            if pos >= longest:
+                break
+        return self._finish(single, found, bands, thrs, overs)
+
+    def push_rows(self, band_db):
+        """New band-dB rows [3][nb] (signal, noise 1, noise 2): one array, or a sequence with one
+        entry per stream (None or [3][0] for nothing new).  Returns as ``push`` (no near-tie
+        guard: it needs the samples)."""
+        lib = self.ctx.lib
+        single, xs = self._streams(band_db, 2)
+        rows = []
+        for v in xs:
+            v = np.zeros((3, 0)) if v is None else np.ascontiguousarray(v, dtype=np.float64)
+            if v.ndim != 2 or v.shape[0] != 3:
+                raise ValueError("band_db must be [3][nb] (signal, noise 1, noise 2)")
+            rows.append(v)
+        F, P = self.F, self.P
+        found, bands, thrs, overs = ([[] for _ in range(F)] for _ in range(4))
+        longest = max(v.shape[1] for v in rows)
+        pos = 0
+        while True:
+            parts = [v[:, pos: pos + P] for v in rows]
+            nbs = np.array([p.shape[1] for p in parts], np.int64)
+            buf = np.zeros((F, 3, P))
+            for f, p in enumerate(parts):
+                buf[f, :, : p.shape[1]] = p
+            self.d_band.upload(buf)
+            self.d_len.upload(nbs)
+            _lib.check(lib.msd_live_session_push_rows_dev(self.h, self.d_band.ptr, self.d_len.ptr, int(nbs.max()), P,
+                                                          self.d_met.ptr, self.cap, self.d_counts.ptr, self.d_thr.ptr,
+                                                          self.d_over.ptr, self.d_status.ptr))
+            frozen = np.array([st == _lib.LIVE_STATUS_OVERFLOW for st in self.status])
+            newb = np.where(frozen, 0, nbs)
+            self._collect(found, bands, thrs, overs, False, newb=newb)
+            for f in range(F):
+                bands[f].append(parts[f][:, : int(newb[f])])
+            pos += P
+            if pos >= longest:
+                break
+        return self._finish(single, found, bands, thrs, overs)
+
+    # ---- state
+    def _states(self):
+        st = (_lib.MsdLiveStreamState * self.F)()
+        _lib.check(self.ctx.lib.msd_live_session_state(self.h, 0, self.F, st))
+        return list(st)
+
+    @property
+    def blocks(self):
+        return [int(s.blocks) for s in self._states()]
+
+    @property
+    def raw_state(self):
+        """the device's msd_live_stream_state per stream (state, status, blocks, trig, lock, until,
+        t_start, meteors, retained, remainder)"""
+        return self._states()
+
+    @property
+    def state(self):
+        """per stream, the reference's state object (aggregates.py:4-24)"""
+        out = []
+        for f, s in enumerate(self._states()):
+            if s.state == 0:
+                out.append(StateInitialization())
+            elif s.state == 1:
+                out.append(StateDetection(float(s.lock), float(s.until)))
+            else:
+                h = self.history(f)
+                first = int(s.blocks - s.retained)  # the global block of h[0]
+                out.append(StateTracking(float(s.lock), float(s.t_start), h[int(s.trig) + 1 - first:].tolist()))
+        return out
+
+    def history(self, stream: int = 0) -> np.ndarray:
+        """the over-noise values the GPU retains for a stream (those of its last ``retained`` blocks)"""
+        C = _lib.C
+        out = np.empty(self.H + self.P, np.float64)
+        n = C.c_int64(0)
+        _lib.check(self.ctx.lib.msd_live_session_history(self.h, int(stream), _lib.ptr(out), out.size, C.byref(n)))
+        return out[: n.value].copy()
+
+    def reset(self, stream: int | None = None):
+        """one stream, or all: back to Init at block 0, empty history and remainder, status 0"""
+        _lib.check(self.ctx.lib.msd_live_session_reset(self.h, -1 if stream is None else int(stream)))
+        self._init_host(None if stream is None else int(stream))
+
+    def close(self):
+        if getattr(self, "h", None) is None:
+            return
+        if self.ctx.h:
+            self.ctx.lib.msd_live_session_destroy(self.h)
+            for b in (self.d_x, self.d_off, self.d_len, self.d_counts, self.d_newb, self.d_status, self.d_met,
+                      self.d_band, self.d_thr, self.d_over):
+                b.free()
+        self.h = None
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
 
 
 def welch_psd(x, fs, nperseg=256, noverlap=None, nfft=None, sample_scale: float = 1.0, device: int = 0):
