@@ -25,6 +25,7 @@
 #include <cstdlib>
 #include <vector>
 
+#include "fft_butterfly.h"
 #include "msd_internal.h"
 
 #include <cmath>
@@ -56,53 +57,8 @@ constexpr int F_TABW = 26;
 constexpr int F_LDS = F_TAB_OFF + F_TABW * 64 * 8;
 static_assert(F_LDS <= 160 * 1024, "LDS budget");
 
-__device__ __forceinline__ float2 cadd(float2 a, float2 b) { return make_float2(a.x + b.x, a.y + b.y); }
-__device__ __forceinline__ float2 csub(float2 a, float2 b) { return make_float2(a.x - b.x, a.y - b.y); }
-__device__ __forceinline__ float2 cmul(float2 a, float2 b) {
-    return make_float2(a.x * b.x - a.y * b.y, a.x * b.y + a.y * b.x);
-}
-__device__ __forceinline__ float2 mul_mi(float2 a) { return make_float2(a.y, -a.x); }
-
-__device__ __forceinline__ void dft4(float2 &a0, float2 &a1, float2 &a2, float2 &a3) {
-    const float2 t0 = cadd(a0, a2), t1 = csub(a0, a2), t2 = cadd(a1, a3), t3 = mul_mi(csub(a1, a3));
-    a0 = cadd(t0, t2);
-    a1 = cadd(t1, t3);
-    a2 = csub(t0, t2);
-    a3 = csub(t1, t3);
-}
-
-// second half of a forward 8-point DFT: a_j = v_j + v_{j+4}, b_j = v_j - v_{j+4} given; s = sqrt(1/2)
-// in a VGPR (vgpr_f: as an SGPR or literal operand its multiplies issue slower)
-__device__ __forceinline__ void dft8_tail(float2 *v, float2 a0, float2 a1, float2 a2, float2 a3, float2 b0, float2 b1,
-                                          float2 b2, float2 b3, float s) {
-    b1 = make_float2((b1.x + b1.y) * s, (b1.y - b1.x) * s);
-    b2 = mul_mi(b2);
-    b3 = make_float2((b3.y - b3.x) * s, -(b3.x + b3.y) * s);
-    dft4(a0, a1, a2, a3);
-    dft4(b0, b1, b2, b3);
-    v[0] = a0; v[2] = a1; v[4] = a2; v[6] = a3;
-    v[1] = b0; v[3] = b1; v[5] = b2; v[7] = b3;
-}
-
-// in-place forward DFT of 8 points, natural order in and out
-__device__ __forceinline__ void dft8(float2 *v, float s) {
-    dft8_tail(v, cadd(v[0], v[4]), cadd(v[1], v[5]), cadd(v[2], v[6]), cadd(v[3], v[7]), csub(v[0], v[4]),
-              csub(v[1], v[5]), csub(v[2], v[6]), csub(v[3], v[7]), s);
-}
-
-// dft8 of the windowed points d_j * w_j (componentwise), the window product of v_{j+4} shared
-// by the first-stage sum and difference: 3 ops per component pair instead of 4
-__device__ __forceinline__ void dft8_windowed(float2 *v, const float2 *d, const float2 *w, float s) {
-    float2 a[4], b[4];
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-        const float px = d[j + 4].x * w[j + 4].x, py = d[j + 4].y * w[j + 4].y;
-        a[j] = make_float2(__builtin_fmaf(d[j].x, w[j].x, px), __builtin_fmaf(d[j].y, w[j].y, py));
-        b[j] = make_float2(__builtin_fmaf(d[j].x, w[j].x, -px), __builtin_fmaf(d[j].y, w[j].y, -py));
-    }
-    dft8_tail(v, a[0], a[1], a[2], a[3], b[0], b[1], b[2], b[3], s);
-}
-
+// cadd / csub / cmul / mul_mi, dft4, dft8, dft8_windowed (host-checkable: butterfly_check.cpp)
+using namespace bfly;
 
 // Transpose-scratch layout (float2 index): bit 4 of n flips bits 1 and 3, plus 4 float2 of
 // padding per 32.  Together with the pass-3 lane table below it makes all four transpose
@@ -353,7 +309,9 @@ __global__ __launch_bounds__(F_NW * 64, 1) void stft1024_kernel(
         }
     };
     FileCur prev = cur;
-    bool have_prev = false;
+    // an int pinned in a scalar register at the loop end: as a loop-carried bool it lives as a lane mask,
+    // rebuilt by a select and a compare in every iteration (A/B: -0.4 to -0.7 %)
+    int have_prev = 0;
     const float hs = vgpr_f(0.70710678118654752440f);  // sqrt(1/2) of the DFT8s, in a VGPR
 
     for (int64_t tl = tb;;) {
@@ -587,7 +545,8 @@ __global__ __launch_bounds__(F_NW * 64, 1) void stft1024_kernel(
         if (l == 0) *reinterpret_cast<float2 *>(&tile[tile_at(256, wcol)]) = make_float2(p256[0], p256[1]);
         lds_barrier();  // tile complete
         prev = cur;
-        have_prev = true;
+        have_prev = 1;
+        asm("" : "+s"(have_prev));  // stays a scalar register
         cur = nxt;
         if (!has_next) break;
         if constexpr (DYN) {

@@ -286,6 +286,9 @@ int main(int argc, char **argv) {
         }
     for (size_t v = 0; v < libs.size(); ++v) {
         auto m = libs[v].ms;
+        printf("%s rounds (ms):", libs[v].path.c_str());  // in run order: drift and the A/A spread show here
+        for (double x : m) printf(" %.4f", x);
+        printf("\n");
         std::sort(m.begin(), m.end());
         printf("%-60s min %.4f  median %.4f ms  (%.1f GB/s, frac %.4f)\n", libs[v].path.c_str(), m[0],
                m[m.size() / 2], gbytes / m[m.size() / 2] * 1e3, gbytes / m[m.size() / 2] * 1e3 / 8000.0);
