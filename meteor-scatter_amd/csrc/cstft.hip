@@ -164,13 +164,17 @@ struct CsTune {
 // Thread j holds z[j + 256 r]; the next frame of the same stream needs z[j + 256 (r + SH)],
 // so with SH > 0 it keeps raw[SH..15] (shifted down) and loads only raw[16-SH..15]: each
 // sample is loaded once per workgroup instead of N / hop times.
-// EN: also an upper bound of each frame's total power in 16 partials, etot[i][stride] (partial i =
-// row r of 16 lanes of wave w at 4 w + r): by Parseval the input norm behind the fp32 FFT's per-bin
-// error bound (the C5 detector's delta error bound, msd_iq_band_delta_bound_dev).  Each thread
-// keeps the max of its 16 powers' sum over a group of 4 consecutive frames; at the group's last
-// frame a row DPP reduction gives the row's partial (>= every frame's: a sum of maxima), stored for
-// each frame of the group -- 16 adds and a max per thread and frame, the reduction and 4 stores per
-// 4 frames (per frame: +5.6 % of the kernel, 12.03 -> 12.71 ms at C5)
+// EN: also each frame's total power in 16 partials, etot[i][stride] (partial i = row r of 16 lanes
+// of wave w at 4 w + r): by Parseval the input norm behind the fp32 FFT's per-bin error bound (the
+// C5 detector's delta error bound, msd_iq_band_delta_bound_dev; an upper bound after its factor
+// 1.001).  Each thread sums the 16 powers it stores, a row DPP reduction gives the row's partial,
+// stored per frame.  The partials are the frame's OWN energy: an earlier form kept the maximum
+// over a group of 4 consecutive frames (one reduction per group), still a bound, but a silent or
+// quiet frame next to a loud one -- a dropout's edge, a level step -- then got the loud frame's
+// norm and with it ed = +inf, and one such frame makes every threshold whose window reads it
+// uncertain (tests/test_gpu_certify_stress.py, `dropout`: 2 frames, 657 of 934 decisions).
+// Cost of the reduction and store per frame instead of per group: the kernel 1.81 -> 1.83 ms, the C5
+// step in the fp32-certified mode 4.83 -> 4.88 ms (bench --workload c5 --c5-mode refine, 30 min shard).
 // Detrend (scipy 'constant', before the window): the frame's complex mean m is subtracted from every
 // sample in float32 as (x - hi) - lo, m = hi + lo both exact (IQ<T>::mean2), so the detrended sample
 // is the float32 rounding of the float64 x - m.  A single float32 mean would leave the coherent error
@@ -219,7 +223,6 @@ __global__ __launch_bounds__(CS_T, (CsTune<T, SH>::kWavesPerSimd)) void cstft409
         tw1[r] = g_tw[(tid * r) & (CS_N - 1)];
     }
     float *const ep = EN ? etot + (int64_t)(wave * 4 + (lane >> 4)) * estride : nullptr;  // this row's partials
-    float emax = 0.f;  // EN: max over the frames of the current group of this thread's power sum
     const int q2 = tid >> 4, j1 = tid & 15;   // pass-2 thread: (q, j1)
     const int q3 = tid & 15, k2a = tid >> 4;  // pass-3 thread: t = q + 16 k2a
     __syncthreads();
@@ -347,17 +350,9 @@ __global__ __launch_bounds__(CS_T, (CsTune<T, SH>::kWavesPerSimd)) void cstft409
                 __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(uint32_t, pw), rsrc, 4 * tid, 1024 * k2b, 2 /* nt */);
                 if constexpr (EN) esum += pw;
             }
-            if constexpr (EN) {
-                emax = fmaxf(emax, esum);
-                // groups of 4 frames from the workgroup's first (per is a multiple of 4): flush at
-                // the group's last frame or the segment's
-                const int64_t gr = g - g0;
-                if ((gr & 3) == 3 || g + 1 == gv) {
-                    const float e = row_sum_f(emax);
-                    if ((lane & 15) == 0)  // the group's frames in this segment
-                        for (int64_t q = (g - (gr & 3) > ga ? g - (gr & 3) : ga); q <= g; ++q) ep[q] = e;
-                    emax = 0.f;
-                }
+            if constexpr (EN) {  // this frame's own energy: the row's partial
+                const float e = row_sum_f(esum);
+                if ((lane & 15) == 0) ep[g] = e;
             }
             // no barrier at the end: the next frame writes buf (and, PD 0, red) only after its first
             // barrier, which every wave reaches after its pass-3 reads of this frame
@@ -506,7 +501,7 @@ int msd_cstft_psd_fsums_dev(msd_cstft_plan *p, const void *x, int dtype, const i
     auto launch = [&](auto kern, const auto *xp) -> int {
         int64_t wgs = grid(kern);
         int64_t per = (total + wgs - 1) / wgs;
-        if (etot) per = (per + 3) / 4 * 4;  // energy groups of 4 frames start at every workgroup's first
+        if (etot) per = (per + 3) / 4 * 4;  // (ranges of whole groups of 4 frames, as the timings were taken)
         wgs = (total + per - 1) / per;
         KernelTimer timer(p->ctx, K_CSTFT);  // the FFT kernel alone: the roofline's
         hipLaunchKernelGGL(kern, dim3((unsigned)wgs), dim3(CS_T), 0, p->ctx->stream, xp, off, len, nstreams,
@@ -514,7 +509,7 @@ int msd_cstft_psd_fsums_dev(msd_cstft_plan *p, const void *x, int dtype, const i
                            msd_cstft_energy_stride(nstreams, max_frames), fsum, nullptr, (int64_t)0, nullptr);
         return MSD_OK;
     };
-    // DYN: the guided schedule (multiples of 4 frames: the energy groups), built when (total, wgs)
+    // DYN: the guided schedule (chunks of multiples of 4 frames), built when (total, wgs)
     // change, and the ticket zeroed on the stream before every launch
     auto launch_dyn = [&](auto kern, const auto *xp) -> int {
         const int64_t wgs = grid(kern);
