@@ -9,7 +9,8 @@
 //     mlab.py:299-356: symmetric Hann, no detrend, pad_to = NFFT).
 //
 // Mapping: one 256-thread workgroup per (file, frame column).  The frame's nperseg samples are
-// read coalesced, detrended (constant: mean in float64 from exact per-thread sums), windowed
+// read coalesced, detrended (constant: mean in float64, exact sums for integer samples, a second
+// pass over the residual for float ones), windowed
 // and packed as M = nfft/2 complex points z[m] = x[2m] + i x[2m+1] (zeros past nperseg) into
 // LDS; radix-4 Stockham passes (one radix-2 pass when log2 M is odd) run between two LDS
 // buffers; the real spectrum is split out with the half-length post-twiddle and |X|^2 * scale
@@ -70,6 +71,19 @@ __device__ __forceinline__ C mul_mi(C a) {  // a * (-i)
 template <typename T>
 __device__ __forceinline__ double sample_d(const T *p, int64_t i) {
     return static_cast<double>(p[i]);
+}
+
+// the workgroup's sum of v, the same value in every thread (red: SA_THREADS / 64 doubles of LDS, not
+// reused before every thread has passed another barrier)
+__device__ __forceinline__ double block_sum(double v, double *red) {
+#pragma unroll
+    for (int o = 32; o >= 1; o >>= 1) v += __shfl_xor(v, o, 64);
+    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
+    __syncthreads();
+    double tot = 0.0;
+#pragma unroll
+    for (int w = 0; w < SA_THREADS / 64; ++w) tot += red[w];
+    return tot;
 }
 
 // one Stockham pass of radix R (4 or 2) over M points: src -> dst, Ns = product of the radices
@@ -159,7 +173,7 @@ __global__ __launch_bounds__(SA_THREADS) void stft_any_kernel(
     extern __shared__ __attribute__((aligned(16))) char smem[];
     C *A = reinterpret_cast<C *>(smem);
     C *B = INPLACE ? A : A + M;
-    __shared__ double red[SA_THREADS / 64];
+    __shared__ double red[2][SA_THREADS / 64];  // the two sums of the detrend
 
     const int64_t f = blockIdx.y;
     const int64_t t = blockIdx.x;
@@ -173,29 +187,31 @@ __global__ __launch_bounds__(SA_THREADS) void stft_any_kernel(
     }
     const T *xf = x + off[f] + t * (int64_t)hop;
 
-    // ---- constant detrend: the mean of the nperseg samples, float64 (exact for integer samples)
-    double mean = 0.0;
+    // ---- constant detrend: the mean of the nperseg samples in float64, subtracted in two parts.
+    // Integer samples: the per-thread and workgroup sums are exact, `mean` is the quotient's float64
+    // rounding and x - mean is formed in float64.  Float samples: a float64 sum of nperseg values near m
+    // is off by several ulp of nperseg m, so `mean` alone leaves that residue as a DC term under a
+    // variation far smaller than the offset (0.6 + 1e-4 randn, nperseg 4096: 1e-3 of the frame in
+    // bins 0 and 1); a second pass takes mlo, the mean of x - mean, whose terms are exact differences
+    // (x within a factor 2 of mean) and whose partial sums are of the variation's size
+    double mean = 0.0, mlo = 0.0;
     if (detrend) {
         double s = 0.0;
         for (int i = threadIdx.x; i < nperseg; i += SA_THREADS) s += sample_d(xf, i);
-#pragma unroll
-        for (int o = 32; o >= 1; o >>= 1) s += __shfl_xor(s, o, 64);
-        if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = s;
-        __syncthreads();
-        double tot = 0.0;
-#pragma unroll
-        for (int w = 0; w < SA_THREADS / 64; ++w) tot += red[w];
-        mean = tot / (double)nperseg;
+        mean = block_sum(s, red[0]) / (double)nperseg;
+        if constexpr (std::is_floating_point<T>::value) {
+            double r = 0.0;
+            for (int i = threadIdx.x; i < nperseg; i += SA_THREADS) r += sample_d(xf, i) - mean;
+            mlo = block_sum(r, red[1]) / (double)nperseg;
+        }
     }
-    // ---- windowed, zero-padded, packed into M complex points.  scipy's constant detrend runs in
-    // float64 for every input but float32 (scipy.signal.detrend casts to 'd'): x - mean in float64,
-    // then rounded to the working precision (a float32 mean of a large DC offset, e.g. uint16 input
-    // around 32768, would leave up to half an ulp of 32768 in bins 0 and 1)
-    constexpr bool f32_detrend = std::is_same<T, float>::value;
-    auto centred = [&](int i) -> R {
-        if constexpr (f32_detrend) return static_cast<R>(xf[i]) - static_cast<R>(mean);
-        else return static_cast<R>(static_cast<double>(xf[i]) - mean);
-    };
+    // ---- windowed, zero-padded, packed into M complex points: (x - mean) - mlo in float64, then
+    // rounded to the working precision -- the float32 (float64) rounding of x - mean for every sample
+    // type.  (A single float32 mean would leave up to half an ulp of the offset in bins 0 and 1:
+    // uint16 input around 32768, float32 input with a DC offset.  scipy detrends float32 input in
+    // float32 and is itself 5e-4 from the float64 result there; the bar is the float64 spectrogram
+    // of the same samples.)
+    auto centred = [&](int i) -> R { return static_cast<R>((sample_d(xf, i) - mean) - mlo); };
     for (int m = threadIdx.x; m < M; m += SA_THREADS) {
         const int i0 = 2 * m, i1 = 2 * m + 1;
         const R a = i0 < nperseg ? centred(i0) * win[i0] : R(0);
