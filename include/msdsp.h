@@ -71,8 +71,7 @@ int msd_memset_dev(msd_ctx *ctx, void *dst, int value, size_t bytes);
 /* Options: MSD_OPT_GENERIC_STFT = 1 → use the generic STFT kernel even where a
  * specialised one exists (A/B testing of the kernels; results must agree).
  * MSD_OPT_FRESH_ALL = 1 → the C5 stream detector computes every adaptive threshold exactly up
- * front instead of only where a scan reads it (A/B of that scheme; results must agree; also
- * set by MSD_FRESH_ALL=1 in the environment).
+ * front instead of only where a scan reads it (A/B of that scheme; results must agree).
  * MSD_OPT_REFINE_GOERTZEL = 1 → msd_iq_delta64_dev computes int16 blocks with the float64
  * Goertzel kernel instead of the exact int8-MFMA one (A/B; both within their bounds).
  * MSD_OPT_CSTFT_RESERVE = n → the persistent C5 spectrogram kernel (msd_cstft_psd_dev) leaves n
@@ -85,18 +84,24 @@ int msd_memset_dev(msd_ctx *ctx, void *dst, int value, size_t bytes);
  * MSD_OPT_CSTFT_SCHED = 0 / 1 / 2 → how the persistent C5 spectrogram kernel (hop 1024) splits the
  * frames over its workgroups: 0 (default) and 2 chunks drawn from a guided schedule by an atomic
  * ticket; 1 one fixed range per workgroup (round-4 behaviour, A/B).  Same output either way.
- * (MSD_CSTFT_SCHED=static|chunked in the environment sets the default of new contexts, for A/B.)
  * MSD_OPT_STFT_SCHED = 0 / 1 / 2 → the same choice for stft1024_kernel's 32-frame tiles (the C3
- * spectrogram): 0 (default) and 1 fixed ranges, 2 chunks (MSD_STFT_SCHED=static|chunked).
+ * spectrogram): 0 (default) and 1 fixed ranges, 2 chunks.
  * MSD_OPT_BLOCK_GOERTZEL = 1 → msd_block_delta[_dev] computes int16 blocks with the float64
  * Goertzel kernel instead of the exact int8-MFMA one (plans with min(block_size, n_fft) = 256,
  * 512 or 1024 and at most 8 band + noise bins take the latter by default; A/B, both within the
- * near-tie bound of meteorgpu/margin.py; MSD_BLOCK_GOERTZEL=1 in the environment sets it for new
- * contexts).
+ * near-tie bound of meteorgpu/margin.py).
  * MSD_OPT_WELCH_GOERTZEL = 1 → msd_welch_bands[_dev] / msd_welch_psd compute int16 samples with the
  * float64 Goertzel kernel instead of the exact int8-MFMA one (plans with nperseg a multiple of 64
  * up to 512, <= 16 segments per block and a window in [-1, 1] take the latter by default; A/B,
- * both within margin.py's live bound; MSD_WELCH_GOERTZEL=1 in the environment). */
+ * both within margin.py's live bound).
+ *
+ * Test hooks (per context; results must agree with the default):
+ * MSD_OPT_WELCH_I8_FORM = 0..3 → which form of the int8-MFMA Welch kernel a launch takes.  Bit 0:
+ * the eight-term float64 digit sum even where the plan's bound allows int32 pairs.  Bit 1: the
+ * generic instantiation even for the live default's shape (nperseg 256, 5 segments per block).
+ * Read at launch, so it takes effect on existing plans.  Every form gives bit-identical output.
+ * MSD_OPT_STREAM_EPS_LOG2 = n in 0..1023 → the C5 stream detector's near-tie bound is widened by
+ * 2^n (never narrower than the bound), so more frames are made exact; same decisions. */
 #define MSD_OPT_GENERIC_STFT 1
 #define MSD_OPT_FRESH_ALL 2
 #define MSD_OPT_REFINE_GOERTZEL 3
@@ -106,6 +111,8 @@ int msd_memset_dev(msd_ctx *ctx, void *dst, int value, size_t bytes);
 #define MSD_OPT_STFT_SCHED 7
 #define MSD_OPT_BLOCK_GOERTZEL 8
 #define MSD_OPT_WELCH_GOERTZEL 9
+#define MSD_OPT_WELCH_I8_FORM 10
+#define MSD_OPT_STREAM_EPS_LOG2 11
 int msd_set_option(msd_ctx *ctx, int option, int value);
 
 /* Per-kernel device timing with HIP events on the context stream.

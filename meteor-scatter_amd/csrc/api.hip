@@ -5,7 +5,6 @@
 #include <rccl/rccl.h>
 
 #include <cmath>
-#include <cstdlib>
 #include <cstring>
 #include <mutex>
 #include <map>
@@ -163,14 +162,6 @@ int msd_create(int device, msd_ctx **out) {
         c->num_cu <= 0)
         c->num_cu = 256;  // grid sizing only: a wrong count costs balance, not correctness
     c->num_cu_dev = c->num_cu;
-    if (const char *e = getenv("MSD_CSTFT_SCHED"))  // A/B runs: static | chunked (MSD_OPT_CSTFT_SCHED)
-        c->cstft_sched = !strcmp(e, "static") ? 1 : !strcmp(e, "chunked") ? 2 : 0;
-    if (const char *e = getenv("MSD_STFT_SCHED"))  // the same for stft1024_kernel (MSD_OPT_STFT_SCHED)
-        c->stft_sched = !strcmp(e, "static") ? 1 : !strcmp(e, "chunked") ? 2 : 0;
-    if (const char *e = getenv("MSD_BLOCK_GOERTZEL"))  // A/B runs: MSD_OPT_BLOCK_GOERTZEL
-        c->block_goertzel = atoi(e) != 0;
-    if (const char *e = getenv("MSD_WELCH_GOERTZEL"))  // A/B runs: MSD_OPT_WELCH_GOERTZEL
-        c->welch_goertzel = atoi(e) != 0;
     hipError_t e = hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking);
     if (e != hipSuccess) {
         delete c;
@@ -298,6 +289,15 @@ int msd_set_option(msd_ctx *ctx, int option, int value) {
             ctx->stream_cus = value;
             return MSD_OK;
         }
+        case MSD_OPT_WELCH_I8_FORM:
+            if (value < 0 || value > 3) return fail(MSD_ERR_INVALID, "msd_set_option: MSD_OPT_WELCH_I8_FORM is 0..3");
+            ctx->welch_i8_form = value;
+            return MSD_OK;
+        case MSD_OPT_STREAM_EPS_LOG2:
+            if (value < 0 || value > 1023)
+                return fail(MSD_ERR_INVALID, "msd_set_option: MSD_OPT_STREAM_EPS_LOG2 is 0..1023");
+            ctx->stream_eps_log2 = value;
+            return MSD_OK;
         default: return fail(MSD_ERR_INVALID, "msd_set_option: unknown option");
     }
 }

@@ -30,38 +30,18 @@
 #include <cstring>
 #include <vector>
 
+#include "i8_digits.h"
 #include "msd_internal.h"
 #include "np_reduce.h"
 
 namespace msd {
 namespace {
 
-typedef int v4i __attribute__((ext_vector_type(4)));
-typedef unsigned v4u __attribute__((ext_vector_type(4)));
-
 constexpr int BI_ND = 7;       // coefficient digits (= column tiles)
 constexpr int BI_ROWS = 16;    // blocks per tile
 constexpr int BI_MAXBINS = 8;  // components 2 * bins <= 16 columns
 constexpr int BI_PP = 9;       // powers row pitch (doubles): 16 rows on 16 disjoint bank pairs for the band sums
 constexpr int BI_WAVES = 8;    // waves per workgroup (2 per SIMD) sharing one copy of the B fragments
-
-template <int CTRL>
-__device__ __forceinline__ double dpp64(double x) {
-    const long long v = __builtin_bit_cast(long long, x);
-    const int lo = __builtin_amdgcn_mov_dpp((int)(v & 0xffffffffll), CTRL, 0xf, 0xf, true);
-    const int hi = __builtin_amdgcn_mov_dpp((int)(v >> 32), CTRL, 0xf, 0xf, true);
-    return __builtin_bit_cast(double, ((long long)hi << 32) | (unsigned)lo);
-}
-
-// A fragments of one K step from the lane's 16 samples (w[0..7]: two per dword): high bytes
-// h = x >> 8 and low bytes l' = (x & 255) - 128 (offset-binary byte ^ 0x80), both as int8
-__device__ __forceinline__ void digits(const uint32_t *w, v4i &hi, v4i &lo) {
-#pragma unroll
-    for (int o = 0; o < 4; ++o) {
-        hi[o] = (int)__builtin_amdgcn_perm(w[2 * o + 1], w[2 * o], 0x07050301u);
-        lo[o] = (int)(__builtin_amdgcn_perm(w[2 * o + 1], w[2 * o], 0x06040200u) ^ 0x80808080u);
-    }
-}
 
 // energy[g] = (sum |X_k|^2 over the band + 1e-12, the same over the noise band) for every block g
 // of files [0, nfiles) x [0, blocks_per_file) (blocks past a file's len / B are skipped; energy
@@ -208,18 +188,6 @@ __global__ __launch_bounds__(64 * BI_WAVES, 1) void block_band_i8_kernel(const i
     }
 }
 
-// one balanced base-256 digit expansion of T (|T| <= 2^54): T = sum_b d[b] 256^(6 - b); false if T
-// does not fit the seven digits (a carry left over)
-bool balanced_digits(int64_t T, int8_t (&d)[BI_ND]) {
-    for (int b = BI_ND - 1; b >= 0; --b) {
-        int64_t r = ((T % 256) + 256) % 256;
-        if (r >= 128) r -= 256;
-        d[b] = (int8_t)r;
-        T = (T - r) / 256;
-    }
-    return T == 0;
-}
-
 }  // namespace
 
 bool block_i8_shape(int64_t L, int nbins) { return (L == 256 || L == 512 || L == 1024) && nbins >= 1 && nbins <= BI_MAXBINS; }
@@ -255,14 +223,14 @@ int block_i8_build(msd_block_plan *p, const double *window, const int *bins, int
         }
     }
     // fragment [b][ks][lane]: lane (column c = lane & 15, group g = lane >> 4), byte j = sample
-    // 64 ks + 8 g + j (j < 8) or 64 ks + 32 + 8 g + (j - 8): the A fragments' order
+    // frag_sample(ks, g, j): the A fragments' order
     std::vector<int8_t> frag((size_t)BI_ND * KS * 64 * 16, 0);
     for (int b = 0; b < BI_ND; ++b)
         for (int ks = 0; ks < KS; ++ks)
             for (int lane = 0; lane < 64; ++lane) {
                 const int cc = lane & 15, g = lane >> 4;
                 for (int j = 0; j < 16; ++j) {
-                    const int n = 64 * ks + (j < 8 ? 8 * g + j : 32 + 8 * g + (j - 8));
+                    const int n = frag_sample(ks, g, j);
                     frag[(((size_t)b * KS + ks) * 64 + lane) * 16 + j] = dig[((size_t)b * 16 + cc) * L + n];
                 }
             }

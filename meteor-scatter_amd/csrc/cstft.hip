@@ -19,10 +19,9 @@
 #include <algorithm>
 #include <cmath>
 #include <cstddef>
-#include <cstdio>
-#include <cstdlib>
 #include <type_traits>
 
+#include "fft_butterfly.h"
 #include "msd_internal.h"
 
 namespace msd {
@@ -38,47 +37,9 @@ constexpr int CS_N = 4096;             // frame length
 constexpr int CS_P = 272;
 constexpr int CS_LDS_F2 = 16 * CS_P;   // float2 per frame buffer (= 256 * 17)
 
-__device__ __forceinline__ float2 c_add(float2 a, float2 b) { return make_float2(a.x + b.x, a.y + b.y); }
-__device__ __forceinline__ float2 c_sub(float2 a, float2 b) { return make_float2(a.x - b.x, a.y - b.y); }
-__device__ __forceinline__ float2 c_mul(float2 a, float2 b) {
-    return make_float2(a.x * b.x - a.y * b.y, a.x * b.y + a.y * b.x);
-}
-__device__ __forceinline__ float2 c_mi(float2 a) { return make_float2(a.y, -a.x); }  // a * (-i)
-
-__device__ __forceinline__ void dft4(float2 &a0, float2 &a1, float2 &a2, float2 &a3) {
-    const float2 t0 = c_add(a0, a2), t1 = c_sub(a0, a2), t2 = c_add(a1, a3), t3 = c_mi(c_sub(a1, a3));
-    a0 = c_add(t0, t2);
-    a1 = c_add(t1, t3);
-    a2 = c_sub(t0, t2);
-    a3 = c_sub(t1, t3);
-}
-
-// forward 16-point DFT, natural order in and out: n = n1 + 4 n2, k = k2 + 4 k1
-__device__ __forceinline__ void dft16(float2 *v) {
-    const float c1 = 0.92387953251128675613f, s1 = 0.38268343236508977173f, h = 0.70710678118654752440f;
-#pragma unroll
-    for (int n1 = 0; n1 < 4; ++n1) dft4(v[n1], v[n1 + 4], v[n1 + 8], v[n1 + 12]);  // v[n1 + 4 k2]
-    // twiddles W16^(n1 k2)
-    v[5] = c_mul(v[5], make_float2(c1, -s1));    // n1 1, k2 1: W^1
-    v[9] = c_mul(v[9], make_float2(h, -h));      // n1 1, k2 2: W^2
-    v[13] = c_mul(v[13], make_float2(s1, -c1));  // n1 1, k2 3: W^3
-    v[6] = c_mul(v[6], make_float2(h, -h));      // n1 2, k2 1: W^2
-    v[10] = c_mi(v[10]);                         // n1 2, k2 2: W^4 = -i
-    v[14] = c_mul(v[14], make_float2(-h, -h));   // n1 2, k2 3: W^6
-    v[7] = c_mul(v[7], make_float2(s1, -c1));    // n1 3, k2 1: W^3
-    v[11] = c_mul(v[11], make_float2(-h, -h));   // n1 3, k2 2: W^6
-    v[15] = c_mul(v[15], make_float2(-c1, s1));  // n1 3, k2 3: W^9
-#pragma unroll
-    for (int k2 = 0; k2 < 4; ++k2) dft4(v[4 * k2], v[4 * k2 + 1], v[4 * k2 + 2], v[4 * k2 + 3]);
-    // v[4 k2 + k1] holds X[k2 + 4 k1]: reorder to natural
-    float2 o[16];
-#pragma unroll
-    for (int k2 = 0; k2 < 4; ++k2)
-#pragma unroll
-        for (int k1 = 0; k1 < 4; ++k1) o[k2 + 4 * k1] = v[4 * k2 + k1];
-#pragma unroll
-    for (int i = 0; i < 16; ++i) v[i] = o[i];
-}
+using bfly::cmul;
+using bfly::csub;
+using bfly::dft16;
 
 template <typename T>
 struct IQ;
@@ -270,7 +231,7 @@ __global__ __launch_bounds__(CS_T, (CsTune<T, SH>::kWavesPerSimd)) void cstft409
             if constexpr (REF) {
                 if (detrend) {
 #pragma unroll
-                    for (int r = 0; r < 16; ++r) v[r] = c_sub(v[r], xref);
+                    for (int r = 0; r < 16; ++r) v[r] = csub(v[r], xref);
                 }
             }
             if constexpr (PD == 0) {
@@ -319,7 +280,7 @@ __global__ __launch_bounds__(CS_T, (CsTune<T, SH>::kWavesPerSimd)) void cstft409
             // ---- pass 1: DFT over r, twiddle W4096^(j q), y[q][j]
             dft16(v);
 #pragma unroll
-            for (int q = 1; q < 16; ++q) v[q] = c_mul(v[q], tw1[q]);
+            for (int q = 1; q < 16; ++q) v[q] = cmul(v[q], tw1[q]);
             if constexpr (PD == 2) lds_barrier();  // everyone has read the previous frame's pass-2 layout
 #pragma unroll
             for (int q = 0; q < 16; ++q) buf[q * CS_P + tid] = v[q];
@@ -329,7 +290,7 @@ __global__ __launch_bounds__(CS_T, (CsTune<T, SH>::kWavesPerSimd)) void cstft409
             for (int j2 = 0; j2 < 16; ++j2) v[j2] = buf[q2 * CS_P + j1 + 16 * j2];
             dft16(v);
 #pragma unroll
-            for (int k = 1; k < 16; ++k) v[k] = c_mul(v[k], tw2[W4 ? 16 * k + j1 : (j1 * k) & 255]);
+            for (int k = 1; k < 16; ++k) v[k] = cmul(v[k], tw2[W4 ? 16 * k + j1 : (j1 * k) & 255]);
             lds_barrier();  // everyone has read pass 1's layout
 #pragma unroll
             for (int k = 0; k < 16; ++k) buf[(16 * k + j1) * 17 + q2] = v[k];  // u[q][k2a][j1], column-major
@@ -515,16 +476,11 @@ int msd_cstft_psd_fsums_dev(msd_cstft_plan *p, const void *x, int dtype, const i
         const int64_t wgs = grid(kern);
         if (p->sched_total != total || p->sched_wgs != wgs) {
             std::vector<int64_t> st(1, 0);
-            // guided: each chunk 1 / (div * wgs) of what is left, at least cmin frames (A/B knobs:
-            // MSD_CSTFT_GUIDE="cmin,div"; bench C5 on one box, profiles/r5_c5_sched_overlap.txt: div 1
-            // 13.06 ms, 2 10.19, 4 9.73-9.81, 8 9.81, 16 9.88; fixed 16 / 32 / 64 / 128-frame chunks
-            // 9.95 / 9.91 / 9.94 / 10.02 -- the workgroups working on nearby frames, not only the
-            // balance, pays)
-            int64_t cmin = 16, div = 4;
-            if (const char *e = getenv("MSD_CSTFT_GUIDE")) {
-                long a = 0, b = 0;
-                if (sscanf(e, "%ld,%ld", &a, &b) == 2 && a >= 4 && b >= 1) cmin = a, div = b;
-            }
+            // guided: each chunk 1 / (div * wgs) of what is left, at least cmin frames (bench C5 on
+            // one box, profiles/r5_c5_sched_overlap.txt: div 1 13.06 ms, 2 10.19, 4 9.73-9.81, 8 9.81,
+            // 16 9.88; fixed 16 / 32 / 64 / 128-frame chunks 9.95 / 9.91 / 9.94 / 10.02 -- the
+            // workgroups working on nearby frames, not only the balance, pays)
+            constexpr int64_t cmin = 16, div = 4;
             for (int64_t pos = 0; pos < total;) {
                 int64_t sz = (total - pos) / (div * wgs);
                 sz = (std::max<int64_t>(sz, cmin) + 3) / 4 * 4;

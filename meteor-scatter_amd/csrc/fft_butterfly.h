@@ -1,5 +1,5 @@
-// Radix-4 / radix-8 butterflies of the STFT kernels (stft1024.hip), in registers, natural order in
-// and out.  Compiles for the device (hipcc) and for a plain host compiler, so the arithmetic can be
+// Radix-4 / radix-8 / radix-16 butterflies of the STFT kernels (stft.hip, stft1024.hip, cstft.hip), in
+// registers, natural order in and out.  Compiles for the device (hipcc) and for a plain host compiler, so the arithmetic can be
 // checked on a CPU against a long-double DFT (butterfly_check.cpp).
 #pragma once
 
@@ -24,7 +24,7 @@ MSD_BFLY_FN float2 csub(float2 a, float2 b) { return make_float2(a.x - b.x, a.y 
 MSD_BFLY_FN float2 cmul(float2 a, float2 b) {
     return make_float2(a.x * b.x - a.y * b.y, a.x * b.y + a.y * b.x);
 }
-MSD_BFLY_FN float2 mul_mi(float2 a) { return make_float2(a.y, -a.x); }
+MSD_BFLY_FN float2 mul_mi(float2 a) { return make_float2(a.y, -a.x); }  // a * (-i)
 
 MSD_BFLY_FN void dft4(float2 &a0, float2 &a1, float2 &a2, float2 &a3) {
     const float2 t0 = cadd(a0, a2), t1 = csub(a0, a2), t2 = cadd(a1, a3), t3 = mul_mi(csub(a1, a3));
@@ -32,6 +32,33 @@ MSD_BFLY_FN void dft4(float2 &a0, float2 &a1, float2 &a2, float2 &a3) {
     a1 = cadd(t1, t3);
     a2 = csub(t0, t2);
     a3 = csub(t1, t3);
+}
+
+// forward 16-point DFT, natural order in and out: n = n1 + 4 n2, k = k2 + 4 k1
+MSD_BFLY_FN void dft16(float2 *v) {
+    const float c1 = 0.92387953251128675613f, s1 = 0.38268343236508977173f, h = 0.70710678118654752440f;
+    MSD_BFLY_UNROLL
+    for (int n1 = 0; n1 < 4; ++n1) dft4(v[n1], v[n1 + 4], v[n1 + 8], v[n1 + 12]);  // v[n1 + 4 k2]
+    // twiddles W16^(n1 k2)
+    v[5] = cmul(v[5], make_float2(c1, -s1));    // n1 1, k2 1: W^1
+    v[9] = cmul(v[9], make_float2(h, -h));      // n1 1, k2 2: W^2
+    v[13] = cmul(v[13], make_float2(s1, -c1));  // n1 1, k2 3: W^3
+    v[6] = cmul(v[6], make_float2(h, -h));      // n1 2, k2 1: W^2
+    v[10] = mul_mi(v[10]);                      // n1 2, k2 2: W^4 = -i
+    v[14] = cmul(v[14], make_float2(-h, -h));   // n1 2, k2 3: W^6
+    v[7] = cmul(v[7], make_float2(s1, -c1));    // n1 3, k2 1: W^3
+    v[11] = cmul(v[11], make_float2(-h, -h));   // n1 3, k2 2: W^6
+    v[15] = cmul(v[15], make_float2(-c1, s1));  // n1 3, k2 3: W^9
+    MSD_BFLY_UNROLL
+    for (int k2 = 0; k2 < 4; ++k2) dft4(v[4 * k2], v[4 * k2 + 1], v[4 * k2 + 2], v[4 * k2 + 3]);
+    // v[4 k2 + k1] holds X[k2 + 4 k1]: reorder to natural
+    float2 o[16];
+    MSD_BFLY_UNROLL
+    for (int k2 = 0; k2 < 4; ++k2)
+        MSD_BFLY_UNROLL
+        for (int k1 = 0; k1 < 4; ++k1) o[k2 + 4 * k1] = v[4 * k2 + k1];
+    MSD_BFLY_UNROLL
+    for (int i = 0; i < 16; ++i) v[i] = o[i];
 }
 
 // second half of a forward 8-point DFT: a_j = v_j + v_{j+4}, b_j = v_j - v_{j+4} given; s = sqrt(1/2)

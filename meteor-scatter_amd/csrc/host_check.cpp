@@ -1,7 +1,7 @@
 // CPU-only sanitizer harness for libmsdsp's host C++ that parses untrusted input or plans device
 // work (SURVEY §5 "race detection / sanitizers"): built with g++ -fsanitize=address,undefined by
-// `make -C meteor-scatter_amd/csrc sanitize` (no HIP; the same headers ingest.hip, stream.hip and
-// refine.hip compile), driven by tests/test_sanitize.py.
+// `make -C meteor-scatter_amd/csrc sanitize` (no HIP; the same headers ingest.hip, stream.hip,
+// refine.hip and the int8-MFMA files compile), driven by tests/test_sanitize.py.
 //   host_check wav FILE            parse + decode FILE (wav_parse.h) with pread, as msd_wav_probe /
 //                                  msd_wav_read do: "ok rate channels bits format dtype container
 //                                  frames data_offset data_bytes fnv1a64" or "err CODE MESSAGE";
@@ -13,10 +13,13 @@
 //                                  refine_plan.h for frame ranges [A, B): checks the block mapping
 //   host_check fuzz SEED ITERS     mutated / truncated WAV images parsed and decoded in memory,
 //                                  random programs and refinement plans
+//   host_check i8 SEED ITERS       i8_digits.h: balanced_digits<6> / <7> over ITERS random T and the
+//                                  edges, zero_sum_round on detrended Hann coefficients, frag_sample
 #include <fcntl.h>
 #include <unistd.h>
 
 #include <cinttypes>
+#include <cmath>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -24,6 +27,7 @@
 #include <string>
 #include <vector>
 
+#include "i8_digits.h"
 #include "np_program.h"
 #include "refine_plan.h"
 #include "wav_parse.h"
@@ -371,6 +375,120 @@ int cmd_fuzz(uint64_t seed, int64_t iters) {
     return 0;
 }
 
+// balanced_digits<ND>(T): true exactly when T lies in the digits' range [-128 S, 127 S],
+// S = sum_b 256^b; then every digit is an int8 (by type) and the digits reproduce T
+template <int ND>
+bool check_digits(int64_t T, std::string &why) {
+    int64_t S = 0;
+    for (int b = 0; b < ND; ++b) S = S * 256 + 1;
+    const bool fits = T >= -128 * S && T <= 127 * S;
+    int8_t d[ND];
+    const bool ok = msd::balanced_digits<ND>(T, d);
+    if (ok != fits) {
+        why = std::to_string(ND) + " digits: T = " + std::to_string(T) + (ok ? " accepted" : " refused");
+        return false;
+    }
+    if (!ok) return true;
+    int64_t back = 0;
+    for (int b = 0; b < ND; ++b) {
+        if (d[b] < -128 || d[b] > 127) {
+            why = std::to_string(ND) + " digits: a digit of T = " + std::to_string(T) + " outside [-128, 127]";
+            return false;
+        }
+        back = back * 256 + d[b];
+    }
+    if (back != T) {
+        why = std::to_string(ND) + " digits: T = " + std::to_string(T) + " comes back as " + std::to_string(back);
+        return false;
+    }
+    return true;
+}
+
+// welch_i8_build's coefficients of one component: the periodic Hann window of length L times
+// e^{-2 pi i k n / L}, minus its mean (the detrend folded in), rounded by zero_sum_round
+bool check_zero_sum(int L, int k, bool im, std::string &why) {
+    const long double tau = 6.283185307179586476925286766559005768L;
+    std::vector<long double> v(L);
+    long double W = 0.0L;
+    for (int n = 0; n < L; ++n) {
+        const long double w = 0.5L - 0.5L * cosl(tau * n / L);
+        const long double a = tau * (long double)((int64_t)k * n % L) / L;
+        v[n] = im ? -w * sinl(a) : w * cosl(a);
+        W += v[n];
+    }
+    for (int n = 0; n < L; ++n) v[n] -= W / L;
+    std::vector<int64_t> T(L);
+    const std::string at = "nperseg " + std::to_string(L) + " bin " + std::to_string(k) + (im ? " im" : " re");
+    if (!msd::zero_sum_round(v, T)) {
+        why = "zero_sum_round refused " + at;
+        return false;
+    }
+    int64_t sum = 0;
+    for (int n = 0; n < L; ++n) {
+        sum += T[n];
+        if (!(fabsl((long double)T[n] - v[n] * 0x1p53L) < 1.0L)) {
+            why = "zero_sum_round: |T - v 2^53| >= 1 at " + at + " n " + std::to_string(n);
+            return false;
+        }
+    }
+    if (sum != 0) {
+        why = "zero_sum_round: sum " + std::to_string(sum) + " at " + at;
+        return false;
+    }
+    return true;
+}
+
+int cmd_i8(uint64_t seed, int64_t iters) {
+    std::string why;
+    auto both = [&](int64_t T) { return check_digits<6>(T, why) && check_digits<7>(T, why); };
+    // the edges: the quantised coefficients' extremes (2^46 refine_i8, 2^54 block_i8 and welch_i8) and
+    // the ends of each digit count's range
+    std::vector<int64_t> edges = {0, 1, -1, 127, 128, -128, -129};
+    for (int64_t m : {int64_t(1) << 46, int64_t(1) << 54, (int64_t(1) << 54) + 1}) edges.push_back(m), edges.push_back(-m);
+    for (int nd : {6, 7}) {
+        int64_t S = 0;
+        for (int b = 0; b < nd; ++b) S = S * 256 + 1;
+        for (int64_t e : {127 * S, 127 * S + 1, -128 * S, -128 * S - 1}) edges.push_back(e);
+    }
+    for (int64_t T : edges)
+        if (!both(T)) {
+            std::printf("bad %s\n", why.c_str());
+            return 1;
+        }
+    std::mt19937_64 g(seed);
+    for (int64_t it = 0; it < iters; ++it) {
+        // every magnitude up to 2^62 (T - r stays inside int64), both signs
+        const int bits = 1 + (int)(g() % 62);
+        const int64_t mag = (int64_t)(g() >> (64 - bits));
+        if (!both(g() & 1 ? mag : -mag)) {
+            std::printf("bad %s\n", why.c_str());
+            return 1;
+        }
+    }
+    for (int L : {64, 256})
+        for (int k : {0, 1, 2, L / 4 - 1, L / 4, L / 2 - 1, L / 2})
+            for (int im = 0; im < 2; ++im)
+                if (!check_zero_sum(L, k, im != 0, why)) {
+                    std::printf("bad %s\n", why.c_str());
+                    return 1;
+                }
+    // frag_sample: (g, j) onto the 64 samples of each K step, one to one
+    for (int ks = 0; ks < 16; ++ks) {
+        bool seen[64] = {};
+        for (int grp = 0; grp < 4; ++grp)
+            for (int j = 0; j < 16; ++j) {
+                const int n = msd::frag_sample(ks, grp, j) - 64 * ks;
+                if (n < 0 || n >= 64 || seen[n]) {
+                    std::printf("bad frag_sample(%d, %d, %d)\n", ks, grp, j);
+                    return 1;
+                }
+                seen[n] = true;
+            }
+    }
+    std::printf("ok %zu edges %" PRId64 " random\n", edges.size(), iters);
+    return 0;
+}
+
 }  // namespace
 
 int main(int argc, char **argv) {
@@ -378,7 +496,8 @@ int main(int argc, char **argv) {
     if (argc >= 3 && !std::strcmp(argv[1], "program")) return cmd_program(std::atoll(argv[2]));
     if (argc >= 9 && !std::strcmp(argv[1], "refine")) return cmd_refine(argc - 2, argv + 2);
     if (argc >= 4 && !std::strcmp(argv[1], "fuzz")) return cmd_fuzz(std::strtoull(argv[2], nullptr, 10), std::atoll(argv[3]));
+    if (argc >= 4 && !std::strcmp(argv[1], "i8")) return cmd_i8(std::strtoull(argv[2], nullptr, 10), std::atoll(argv[3]));
     std::fprintf(stderr, "usage: host_check wav FILE | program N | refine N HOP BLO BHI NLO NHI NSAMP [A B]... | "
-                         "fuzz SEED ITERS\n");
+                         "fuzz SEED ITERS | i8 SEED ITERS\n");
     return 2;
 }

@@ -55,27 +55,12 @@ struct WelchArgs {
     int band_slot0[MSD_WELCH_MAX_BANDS];  // first slot of each band
 };
 
-template <int CTRL>
-__device__ __forceinline__ double dpp_f64(double x) {
-    const int2 v = __builtin_bit_cast(int2, x);
-    int2 r;
-    r.x = __builtin_amdgcn_mov_dpp(v.x, CTRL, 0xf, 0xf, true);
-    r.y = __builtin_amdgcn_mov_dpp(v.y, CTRL, 0xf, 0xf, true);
-    return __builtin_bit_cast(double, r);
-}
-
 __device__ __forceinline__ double readlane_f64(double x, int lane) {
     const int2 v = __builtin_bit_cast(int2, x);
     int2 r;
     r.x = __builtin_amdgcn_readlane(v.x, lane);
     r.y = __builtin_amdgcn_readlane(v.y, lane);
     return __builtin_bit_cast(double, r);
-}
-
-__device__ __forceinline__ void wave_sync() {
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
 }
 
 // np.sum(seg[0:n]) by one wave, numpy's pairwise order.  n = 256 (scipy's default
@@ -89,9 +74,9 @@ __device__ __forceinline__ double wave_np_sum(const double *seg, int n, int lane
             r = a[0];
             for (int k = 1; k < 16; ++k) r += a[8 * k];
         }
-        r += dpp_f64<0xB1>(r);   // lane ^ 1
-        r += dpp_f64<0x4E>(r);   // lane ^ 2
-        r += dpp_f64<0x141>(r);  // half-row mirror: lanes 0-3 meet 4-7 (8-11 meet 12-15)
+        r += dpp64<0xB1>(r);   // lane ^ 1
+        r += dpp64<0x4E>(r);   // lane ^ 2
+        r += dpp64<0x141>(r);  // half-row mirror: lanes 0-3 meet 4-7 (8-11 meet 12-15)
         return 0.0 + (readlane_f64(r, 0) + readlane_f64(r, 8));
     }
     double v = 0.0;
@@ -333,14 +318,8 @@ __global__ __launch_bounds__(WL_THREADS) void live_history_kernel(const int64_t 
 // 0.65-0.70 ms per day.)
 // blocks per segment: 256 against 64 / 128 / 512 / 1024 measured 0.26-0.31 vs 0.55 / 0.34-0.35 /
 // 0.31-0.32 / 0.42-0.47 ms per day for the state machine (profiles/r6_live_seglen_ab.txt)
-#ifndef LV_SEGLEN_N
-#define LV_SEGLEN_N 256
-#endif
-constexpr int LV_SEGLEN = LV_SEGLEN_N;
-#ifndef LV_ROUNDS_N
-#define LV_ROUNDS_N 4
-#endif
-constexpr int LV_ROUNDS = LV_ROUNDS_N;  // rounds launched before the convergence flag is read
+constexpr int LV_SEGLEN = 256;
+constexpr int LV_ROUNDS = 4;  // rounds launched before the convergence flag is read
 
 __device__ __forceinline__ bool live_same_entry(const LiveScan &x, const LiveScan &y, double t1_first) {
     if (x.state != y.state) return false;

@@ -81,6 +81,8 @@ struct msd_ctx {
     int stft_sched = 0;            // MSD_OPT_STFT_SCHED: the same for stft1024_kernel (tiles)
     int num_cu_dev = 0;            // the device's CUs (num_cu: those the stream may use, MSD_OPT_STREAM_CUS)
     int stream_cus = 0;            // MSD_OPT_STREAM_CUS value in force
+    int welch_i8_form = 0;         // MSD_OPT_WELCH_I8_FORM (test hook): bit 0 no int32 pairs, bit 1 generic instantiation
+    int stream_eps_log2 = 0;       // MSD_OPT_STREAM_EPS_LOG2 (test hook): the stream's near-tie bound times 2^n
 };
 
 namespace msd {
@@ -154,7 +156,6 @@ struct msd_welch_plan {
     void *d_i8 = nullptr;
     int i8_nct = 0;
     bool i8_pairs = false;  // the accumulators' digit sums fit int32 pairs (welch_i8_build)
-    bool i8_special = true;  // the live default's shape takes its own instantiation
 };
 
 namespace msd {
@@ -170,6 +171,23 @@ __device__ __forceinline__ int64_t uniform_i64(int64_t v) {
     const uint32_t lo = __builtin_amdgcn_readfirstlane((uint32_t)v);
     const uint32_t hi = __builtin_amdgcn_readfirstlane((uint32_t)((uint64_t)v >> 32));
     return (int64_t)(((uint64_t)hi << 32) | lo);
+}
+
+// wave-level barrier that also orders the wave's LDS accesses across it (one wave's lanes exchanging
+// values through LDS)
+__device__ __forceinline__ void wave_sync() {
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+}
+
+// a float64 from the lane DPP control CTRL selects (two 32-bit DPP moves)
+template <int CTRL>
+__device__ __forceinline__ double dpp64(double x) {
+    const long long v = __builtin_bit_cast(long long, x);
+    const int lo = __builtin_amdgcn_mov_dpp((int)(v & 0xffffffffll), CTRL, 0xf, 0xf, true);
+    const int hi = __builtin_amdgcn_mov_dpp((int)(v >> 32), CTRL, 0xf, 0xf, true);
+    return __builtin_bit_cast(double, ((long long)hi << 32) | (unsigned)lo);
 }
 
 // DPP: v + v[lane ^ 1], v[lane ^ 2], mirrored half rows, mirrored rows → each lane

@@ -37,14 +37,13 @@
 #include <type_traits>
 #include <vector>
 
+#include "i8_digits.h"
 #include "msd_internal.h"
 #include "refine_plan.h"
 #include "refine_i8.h"
 
 namespace msd {
 namespace {
-
-typedef int v4i __attribute__((ext_vector_type(4)));
 
 constexpr int I8_ND = 6;     // twiddle digits
 constexpr int I8_BPT = 4;    // blocks per 16-row tile
@@ -60,28 +59,6 @@ __device__ __forceinline__ int find_range_i8(const int64_t *cs, int nr, int64_t 
         else hi = mid - 1;
     }
     return lo;
-}
-
-template <int CTRL>
-__device__ __forceinline__ double dpp64(double x) {
-    const long long v = __builtin_bit_cast(long long, x);
-    const int lo = __builtin_amdgcn_mov_dpp((int)(v & 0xffffffffll), CTRL, 0xf, 0xf, true);
-    const int hi = __builtin_amdgcn_mov_dpp((int)(v >> 32), CTRL, 0xf, 0xf, true);
-    return __builtin_bit_cast(double, ((long long)hi << 32) | (unsigned)lo);
-}
-typedef unsigned v4u __attribute__((ext_vector_type(4)));
-// the A fragments of K step ks from the lane's dwords w[8 ks .. 8 ks + 7] (values 16 ks .. 16 ks + 15
-// of its chunk): the high bytes (h = x >> 8) and the low bytes minus 128 (l' = (x & 255) ^ 0x80 as int8)
-__device__ __forceinline__ void digits(const uint32_t *w, v4i &hi, v4i &lo, uint32_t &habs) {
-#pragma unroll
-    for (int o = 0; o < 4; ++o) {
-        const uint32_t h = __builtin_amdgcn_perm(w[2 * o + 1], w[2 * o], 0x07050301u);
-        const uint32_t l = __builtin_amdgcn_perm(w[2 * o + 1], w[2 * o], 0x06040200u) ^ 0x80808080u;
-        hi[o] = (int)h;
-        lo[o] = (int)l;
-        // sum |h| over the 4 bytes: |h| = |(h ^ 0x80) - 0x80| on the offset-binary bytes
-        habs = __builtin_amdgcn_sad_u8(h ^ 0x80808080u, 0x80808080u, habs);
-    }
 }
 
 // int sums of lane l and lane l ^ 16 / l ^ 32 (v_permlane16/32_swap: VALU, no LDS round trip)
@@ -308,16 +285,6 @@ __global__ __launch_bounds__(256, 1) void block_i8_kernel(const int16_t *__restr
     flush();
 }
 
-// one balanced base-256 digit expansion of T (|T| <= 2^46): T = sum_b d[b] 256^(5 - b)
-void balanced_digits(int64_t T, int8_t (&d)[I8_ND]) {
-    for (int b = I8_ND - 1; b >= 0; --b) {
-        int64_t r = ((T % 256) + 256) % 256;  // 0..255
-        if (r >= 128) r -= 256;               // -128..127
-        d[b] = (int8_t)r;
-        T = (T - r) / 256;
-    }
-}
-
 }  // namespace
 
 bool i8_supported(const RefineGeom &G, const RefineBins &K) {
@@ -371,8 +338,10 @@ int launch_refine_i8(msd_ctx *ctx, const int16_t *x, const RefineGeom &G, const 
                     // W^{km} = C - i S;  Y = sum (I + i Q)(C - i S): re = I C + Q S, im = Q C - I S
                     const long double val = part == 0 ? ((v & 1) ? S : C) : ((v & 1) ? C : -S);
                     int8_t d[I8_ND];
-                    // T = round(val 2^46) from the long-double value: |T 2^-46 - w| <= 2^-47 (1 + 2^-16)
-                    balanced_digits((int64_t)llroundl(ldexpl(val, 46)), d);
+                    // T = round(val 2^46) from the long-double value: |T 2^-46 - w| <= 2^-47 (1 + 2^-16);
+                    // |T| <= 2^46 fits the six digits
+                    if (!balanced_digits((int64_t)llroundl(ldexpl(val, 46)), d))
+                        return fail(MSD_ERR_INVALID, "refine_i8: twiddle beyond 6 digits");
                     Bm[((size_t)t * KV + v) * 16 + cc] = d[dig];
                     init[t * 16 + cc] += 128 * (int)d[dig];
                 }
@@ -383,7 +352,7 @@ int launch_refine_i8(msd_ctx *ctx, const int16_t *x, const RefineGeom &G, const 
             for (int ks = 0; ks < I8_KS; ++ks)
                 for (int l = 0; l < 64; ++l)
                     for (int j = 0; j < 16; ++j) {  // lane l byte j of step ks (block_i8_kernel's loads)
-                        const int v = 64 * ks + 32 * (j >> 3) + 8 * (l >> 4) + (j & 7);
+                        const int v = frag_sample(ks, l >> 4, j);
                         frag[(((size_t)t * I8_KS + ks) * 64 + l) * 16 + j] = Bm[((size_t)t * KV + v) * 16 + (l & 15)];
                     }
         std::memcpy(tab.data() + nb_frag, init.data(), nb_init);

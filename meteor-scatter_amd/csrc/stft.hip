@@ -14,17 +14,16 @@
 //     16-B stores: out[file][k][t] with a padded row pitch ld (multiple of 32).
 // HBM traffic per frame: hop*sizeof(sample) read (frames overlap; the overlap is
 // served by L2) + K*4 B written.  No MFMA: the op is bandwidth/VALU bound.
+#include "fft_butterfly.h"
 #include "msd_internal.h"
 
 namespace msd {
 namespace {
 
-__device__ __forceinline__ float2 cadd(float2 a, float2 b) { return make_float2(a.x + b.x, a.y + b.y); }
-__device__ __forceinline__ float2 csub(float2 a, float2 b) { return make_float2(a.x - b.x, a.y - b.y); }
-__device__ __forceinline__ float2 cmul(float2 a, float2 b) {
-    return make_float2(a.x * b.x - a.y * b.y, a.x * b.y + a.y * b.x);
-}
-__device__ __forceinline__ float2 mul_mi(float2 a) { return make_float2(a.y, -a.x); }  // a * (-i)
+using bfly::cadd;
+using bfly::cmul;
+using bfly::csub;
+using bfly::mul_mi;
 
 template <int R>
 struct Dft;
@@ -39,12 +38,7 @@ struct Dft<2> {
 template <>
 struct Dft<4> {
     __device__ __forceinline__ static void run(float2 *v) {
-        float2 t0 = cadd(v[0], v[2]), t1 = csub(v[0], v[2]);
-        float2 t2 = cadd(v[1], v[3]), t3 = mul_mi(csub(v[1], v[3]));
-        v[0] = cadd(t0, t2);
-        v[1] = cadd(t1, t3);
-        v[2] = csub(t0, t2);
-        v[3] = csub(t1, t3);
+        bfly::dft4(v[0], v[1], v[2], v[3]);
     }
 };
 template <>
@@ -75,12 +69,6 @@ constexpr int ilog2(int v) { return v <= 1 ? 0 : 1 + ilog2(v / 2); }
 // padded LDS index: 2 float2 of padding per 8 (keeps 16-B alignment of even
 // indices and makes the staging ds_write_b128 and pass accesses conflict-light)
 __device__ __forceinline__ constexpr int phys(int n) { return n + ((n >> 3) << 1); }
-
-__device__ __forceinline__ void wave_sync() {
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-}
 
 // One Stockham autosort pass of radix R over M points held in the wave's scratch
 // S (in place: every lane loads all its butterflies before any lane stores).

@@ -21,15 +21,12 @@
 // persistent and walk a contiguous range of tiles (the half frame shared by
 // neighbouring tiles is re-read from L2); each wave loads its next tile's frame pair
 // into the sample registers as soon as the current pair is windowed.
-#include <cstdio>
-#include <cstdlib>
 #include <vector>
 
 #include "fft_butterfly.h"
 #include "msd_internal.h"
 
 #include <cmath>
-#include <cstdlib>
 #include <type_traits>
 
 namespace msd {
@@ -84,12 +81,6 @@ __constant__ int8_t k_pass3_lane[64] = {0,  32, 1,  63, 3,  61, 5,  59, 6,  58, 
 // banks (tools/lds_bank_model.py checks every access pattern of the kernel).
 __device__ __forceinline__ int tile_rot(int k) { return (k & 39) == 32 ? 16 : 0; }
 __device__ __forceinline__ int tile_at(int k, int c) { return k * F_PITCH + ((c + tile_rot(k)) & 31); }
-
-__device__ __forceinline__ void wave_sync() {
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-}
 
 template <typename T>
 struct PairIO;
@@ -585,11 +576,8 @@ int launch_fast_t(msd_stft_plan *p, const void *x, const int64_t *off, const int
                           : (sh ? stft1024_kernel<T, 0, PairIO<T>::kInt, true> : stft1024_kernel<T, 0, false, true>);
         if (int rc = ensure_dyn_lds(reinterpret_cast<const void *>(dkern), F_LDS)) return rc;
         if (p->sched_total != ntiles || p->sched_wgs != wgs) {
-            int64_t cmin = 2, div = 2;  // A/B knobs: MSD_STFT_GUIDE="cmin,div" (tiles)
-            if (const char *e = getenv("MSD_STFT_GUIDE")) {
-                long a = 0, b = 0;
-                if (sscanf(e, "%ld,%ld", &a, &b) == 2 && a >= 2 && b >= 1) cmin = a, div = b;
-            }
+            // guided: each chunk 1 / (div * wgs) of what is left, at least cmin tiles
+            constexpr int64_t cmin = 2, div = 2;
             std::vector<int64_t> st(1, 0);
             for (int64_t pos = 0; pos < ntiles;) {
                 const int64_t sz = std::max<int64_t>((ntiles - pos) / (div * wgs), cmin);

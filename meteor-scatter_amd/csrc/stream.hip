@@ -33,7 +33,6 @@
 
 #include <algorithm>
 #include <cmath>
-#include <cstdlib>
 #include <cstring>
 #include <type_traits>
 #include <vector>
@@ -335,7 +334,7 @@ struct FreshParams {
     double k;
     int nleaf;
     int64_t pre_per;  // prefix blocks per thread of blockscan_kernel (error bound of the predictor)
-    double eps_scale; // test hook (MSD_STREAM_EPS_SCALE): widens the bound, more frames made exact
+    double eps_scale; // test hook (MSD_OPT_STREAM_EPS_LOG2): widens the bound, more frames made exact
 };
 
 // record i of the program through a pointer typed with its address space (LDS or global int32s, so
@@ -1393,8 +1392,7 @@ static void fresh_params(msd_stream_plan *p, FreshParams &P) {
     P.k = p->cfg.k_std;
     P.nleaf = p->nleaf;
     P.pre_per = (P.x_len / PB + 1 + 1023) / 1024;
-    const char *es = getenv("MSD_STREAM_EPS_SCALE");
-    P.eps_scale = es && atof(es) >= 1.0 ? atof(es) : 1.0;  // never narrower than the bound
+    P.eps_scale = std::ldexp(1.0, p->ctx->stream_eps_log2);  // >= 1: never narrower than the bound
 }
 
 int msd_stream_set_exact_thresholds(msd_stream_plan *p, int32_t on) {
@@ -1423,16 +1421,13 @@ int msd_stream_fresh(msd_stream_plan *p) {
     KernelTimer timer(p->ctx, K_FRESH);
     FreshParams P;
     fresh_params(p, P);
-    // MSD_FRESH_ALL=1: every tile exact up front (A/B timing of the exact kernel; same results)
-    static const bool all = [] {
-        const char *e = getenv("MSD_FRESH_ALL");
-        return e && e[0] == '1';
-    }();
+    // MSD_OPT_FRESH_ALL: every tile exact up front (A/B timing of the exact kernel; same results)
+    const bool all = p->ctx->fresh_all;
     // decisions-only: every frame predicted (with its error bound), exact ones listed by the scan
-    p->decide = !p->want_exact && P.W > 0 && !(all || p->ctx->fresh_all);
-    // need = 0 (1 with MSD_FRESH_ALL), done = 0, exact = 0 (decisions only): one launch
+    p->decide = !p->want_exact && P.W > 0 && !all;
+    // need = 0 (1 with MSD_OPT_FRESH_ALL), done = 0, exact = 0 (decisions only): one launch
     hipLaunchKernelGGL(fresh_clear_kernel, dim3(512), dim3(256), 0, st, p->d_need, p->ntiles,
-                       (all || p->ctx->fresh_all) ? 1 : 0, p->d_done, p->ntiles + 1, p->decide ? p->d_exact : nullptr,
+                       all ? 1 : 0, p->d_done, p->ntiles + 1, p->decide ? p->d_exact : nullptr,
                        p->n_local);
     // frames [0, jshort) have windows shorter than W: exact right away
     int64_t jshort = P.W - p->frame0;

@@ -18,7 +18,7 @@
 // |X| <= 2 sum|x|, 5 u sum|x| -- inside margin.live_over_error's int8 term (18 u nperseg max|x|).
 //
 // GEMM: rows = segments (a 16-row tile holds bpt = 16 / nseg whole blocks, nseg rows each; the
-// 5-segment instantiation walks units of 16 blocks = 5 full tiles, see SUPER),
+// 5-segment instantiation walks units of 16 blocks = 5 full tiles, see NSEG == 5 below),
 // K = nperseg samples in steps of 64 (the lane's A fragment: 16 samples of its row, 8 at 8 g and 8 at
 // 32 + 8 g of the step, g = lane >> 4, as block_i8.hip), columns = the components of the band bins
 // (bin j's real part 2 j, imaginary part 2 j + 1), 16 per column tile.  The B fragments of all bins
@@ -36,6 +36,7 @@
 #include <cstdlib>
 #include <vector>
 
+#include "i8_digits.h"
 #include "msd_internal.h"
 #include "np_reduce.h"
 
@@ -44,46 +45,24 @@
 namespace msd {
 namespace {
 
-typedef int v4i __attribute__((ext_vector_type(4)));
-typedef unsigned v4u __attribute__((ext_vector_type(4)));
-
 constexpr int WI_ND = 7;                  // coefficient digits
 constexpr int WI_NW = 8;                  // accumulator weights 256^0 .. 256^7
-#ifndef WI_WAVES_N
-#define WI_WAVES_N 12
-#endif
-// the digit combination in float64 (two exact Horner groups, one rounding) or in int64: 4.77-4.83
-// vs 5.46-5.49 ms per day, the int64 form's 64-bit shifts and sign extensions cost more VALU issue
-// than the float64 conversions they replace (profiles/r6_welch_i8_epi_ab.txt)
-#ifndef WI_EPI_INT
-#define WI_EPI_INT 0
-#endif
-// the MFMA with the coefficients as its A operand and the samples as B (the fragments' register
-// layouts are the same): the output tile transposed, so a lane holds one segment's re and im of two
-// bins and forms their powers itself (no partner exchange, no selects)
-#ifndef WI_TRANS
-#define WI_TRANS 1
-#endif
-// (the 5-segment instantiation only: the generic one spills 14 registers in this form)
-#define WI_MFMA(samp, coef, acc)                                                                   \
-    (TR ? __builtin_amdgcn_mfma_i32_16x16x64_i8(coef, samp, acc, 0, 0, 0)                         \
-        : __builtin_amdgcn_mfma_i32_16x16x64_i8(samp, coef, acc, 0, 0, 0))
-#ifndef WI_SUPER
-#define WI_SUPER 1
-#endif
-#ifndef WI_SCHED
-#define WI_SCHED 1
-#endif
-#ifndef WI_SPECIAL
-#define WI_SPECIAL 1
-#endif
+// the MFMA of the NSEG > 0 instantiations (TR) takes the coefficients as its A operand and the
+// samples as B (the fragments' register layouts are the same): the output tile transposed, so a lane
+// holds one segment's re and im of two bins and forms their powers itself (no partner exchange, no
+// selects).  The generic instantiation spills 14 registers in that form and keeps the samples as A.
+template <bool TR>
+__device__ __forceinline__ v4i wi_mfma(v4i samp, v4i coef, v4i acc) {
+    return TR ? __builtin_amdgcn_mfma_i32_16x16x64_i8(coef, samp, acc, 0, 0, 0)
+              : __builtin_amdgcn_mfma_i32_16x16x64_i8(samp, coef, acc, 0, 0, 0);
+}
 // an M tile's samples are loaded at its start: prefetching the next tile's into 32 registers
 // during this one measured 4.14-4.17 against 4.11-4.13 ms per day, the other waves hide the load
 // (profiles/r6_welch_i8_epi_ab.txt)
 // waves per workgroup: 12 = 3 per SIMD (<= 168 VGPRs).  Against 8 (2 per SIMD): 5.52-5.55 vs
 // 5.97-6.04 ms per day in the first form (profiles/r6_welch_i8_ab.txt), 4.14-4.17 vs 4.31-4.33 in
 // this one (profiles/r6_welch_i8_epi_ab.txt)
-constexpr int WI_WAVES = WI_WAVES_N;
+constexpr int WI_WAVES = 12;
 // waves per workgroup for KS K steps: 8 K steps (nperseg 512) need 236 VGPRs, 2 waves per SIMD
 constexpr int wi_waves(int KS) { return KS <= 4 ? WI_WAVES : 8; }
 constexpr int WI_PP = 9;                  // per-wave power scratch: 16 rows x 8 bins, pitch 9 doubles
@@ -104,42 +83,11 @@ struct WelchI8Args {
     double rnseg;   // 1 / nseg
 };
 
-template <int CTRL>
-__device__ __forceinline__ double dpp64(double x) {
-    const long long v = __builtin_bit_cast(long long, x);
-    const int lo = __builtin_amdgcn_mov_dpp((int)(v & 0xffffffffll), CTRL, 0xf, 0xf, true);
-    const int hi = __builtin_amdgcn_mov_dpp((int)(v >> 32), CTRL, 0xf, 0xf, true);
-    return __builtin_bit_cast(double, ((long long)hi << 32) | (unsigned)lo);
-}
-
-// A fragments of one K step from the lane's 16 samples (w[0..7], two per dword): h = x >> 8 and
-// l' = (x & 255) - 128 (offset-binary byte ^ 0x80), as int8
-__device__ __forceinline__ void digits(const uint32_t *w, v4i &hi, v4i &lo) {
-#pragma unroll
-    for (int o = 0; o < 4; ++o) {
-        hi[o] = (int)__builtin_amdgcn_perm(w[2 * o + 1], w[2 * o], 0x07050301u);
-        lo[o] = (int)(__builtin_amdgcn_perm(w[2 * o + 1], w[2 * o], 0x06040200u) ^ 0x80808080u);
-    }
-}
-
-// sum_w 256^w a_w rounded once to float64: each group of four exact in int64 (|a| < 2^25: < 2^49),
-// t = hi + (lo >> 32) and r = lo mod 2^32 give sum = t 2^32 + r; t converts exactly (|t| < 2^50)
-#if WI_EPI_INT
-__device__ __forceinline__ int64_t group4(int a0, int a1, int a2, int a3) {
-    int64_t v = a3;
-    v = (v << 8) + a2;
-    v = (v << 8) + a1;
-    return (v << 8) + a0;
-}
-#endif
+// sum_w 256^w a_w rounded once to float64: each group of four is an exact float64 Horner sum
+// (|a| < 2^25: < 2^49), the last fma rounds once.  (The same sum in int64 measured 5.46-5.49 against
+// 4.77-4.83 ms per day: its 64-bit shifts and sign extensions cost more VALU issue than the float64
+// conversions they replace, profiles/r6_welch_i8_epi_ab.txt.)
 __device__ __forceinline__ double digit_sum(int a0, int a1, int a2, int a3, int a4, int a5, int a6, int a7) {
-#if WI_EPI_INT
-    const int64_t lo = group4(a0, a1, a2, a3), hi = group4(a4, a5, a6, a7);
-    const int64_t t = hi + (lo >> 32);
-    const double tf = __builtin_fma((double)(int)(t >> 32), 0x1p32, (double)(uint32_t)t);
-    return __builtin_fma(tf, 0x1p32, (double)(uint32_t)lo);
-#else
-    // the same value in float64: each group's Horner sum is exact (< 2^49), the last fma rounds once
     double lo = (double)a3, hi = (double)a7;
     lo = __builtin_fma(lo, 256.0, (double)a2);
     hi = __builtin_fma(hi, 256.0, (double)a6);
@@ -148,7 +96,6 @@ __device__ __forceinline__ double digit_sum(int a0, int a1, int a2, int a3, int 
     lo = __builtin_fma(lo, 256.0, (double)a0);
     hi = __builtin_fma(hi, 256.0, (double)a4);
     return __builtin_fma(hi, 0x1p32, lo);
-#endif
 }
 
 // the same value when the plan has checked |a_w| + 256 |a_(w+1)| < 2^31 for w = 0, 2, 4, 6 (every
@@ -159,12 +106,6 @@ __device__ __forceinline__ double digit_sum_pairs(int a0, int a1, int a2, int a3
     const double lo = __builtin_fma((double)p1, 65536.0, (double)p0);  // exact: < 2^48
     const double hi = __builtin_fma((double)p3, 65536.0, (double)p2);
     return __builtin_fma(hi, 0x1p32, lo);
-}
-
-__device__ __forceinline__ void wave_sync() {
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
 }
 
 // a block of the batch: file f, block b of the file, its first sample; valid = the block exists
@@ -247,8 +188,8 @@ __global__ __launch_bounds__(64 * wi_waves(KS), 1) void welch_i8_kernel(const in
                                                                     const double *__restrict__ dbl,
                                                                     double *__restrict__ psd) {
     constexpr int NW = wi_waves(KS);
-    constexpr bool TR = WI_TRANS && NSEG > 0;  // the transposed tile (WI_MFMA)
-    constexpr bool SUPER = WI_SUPER && TR && NSEG == 5;  // 16-block units (below)
+    constexpr bool TR = NSEG > 0;      // the transposed tile (wi_mfma)
+    constexpr bool SUPER = NSEG == 5;  // 16-block units (below)
     WelchI8Args A = Ain;
     if constexpr (NSEG > 0) {
         A.nseg = NSEG;
@@ -298,13 +239,11 @@ __global__ __launch_bounds__(64 * wi_waves(KS), 1) void welch_i8_kernel(const in
     };
     v4u R[2 * KS];
     v4i ah[KS], al[KS];  // the current M tile's sample digits
-#if WI_SCHED
     // the B fragments run one K step ahead: digit d of step ks + 1 (or of the next column tile's
     // step 0) is read into bk[d] as soon as step ks's second MFMA on it has issued, 7 MFMAs
     // before its first use, and the MFMA / LDS order is pinned (the scheduler otherwise waits on
     // each fragment right after requesting it)
     v4i bk[WI_ND];
-#endif
     auto load_digits = [&](const int16_t *p) __attribute__((always_inline)) {
 #pragma unroll
         for (int ks = 0; ks < KS; ++ks) R[2 * ks] = fetch(p, ks, 0), R[2 * ks + 1] = fetch(p, ks, 1);
@@ -314,25 +253,24 @@ __global__ __launch_bounds__(64 * wi_waves(KS), 1) void welch_i8_kernel(const in
             __builtin_memcpy(w, &R[2 * ks], 32);
             digits(w, ah[ks], al[ks]);
         }
-#if WI_SCHED
 #pragma unroll
         for (int d = 0; d < WI_ND; ++d) bk[d] = sB[(size_t)(d * KS) * 64 + l];
-#endif
     };
-    // one column tile's MFMAs into acc (the B fragments one K step ahead when WI_SCHED)
+    // one column tile's MFMAs into acc, the B fragments one K step ahead.  h x digit d: weight
+    // 256^(7 - d); l' x digit d: 256^(6 - d) (the l' chain second, so the two MFMAs into one
+    // accumulator are 7 apart)
     auto mm = [&](v4i(&acc)[WI_NW], int j) __attribute__((always_inline)) {
 #pragma unroll
         for (int w = 0; w < WI_NW; ++w) acc[w] = v4i{0, 0, 0, 0};
         const v4i *bj = sB + (size_t)j * WI_ND * KS * 64 + l;
-#if WI_SCHED
         const v4i *bn = j + 1 < nct ? bj + (size_t)WI_ND * KS * 64 : bj;  // the last tile re-reads its own (unused)
 #pragma unroll
         for (int ks = 0; ks < KS; ++ks) {
 #pragma unroll
-            for (int d = 0; d < WI_ND; ++d) acc[7 - d] = WI_MFMA(ah[ks], bk[d], acc[7 - d]);
+            for (int d = 0; d < WI_ND; ++d) acc[7 - d] = wi_mfma<TR>(ah[ks], bk[d], acc[7 - d]);
 #pragma unroll
             for (int d = 0; d < WI_ND; ++d) {
-                acc[6 - d] = WI_MFMA(al[ks], bk[d], acc[6 - d]);
+                acc[6 - d] = wi_mfma<TR>(al[ks], bk[d], acc[6 - d]);
                 bk[d] = ks + 1 < KS ? bj[(d * KS + ks + 1) * 64] : bn[(d * KS) * 64];
             }
             __builtin_amdgcn_sched_group_barrier(0x008, 7, 0);  // the 7 h MFMAs
@@ -342,20 +280,6 @@ __global__ __launch_bounds__(64 * wi_waves(KS), 1) void welch_i8_kernel(const in
                 __builtin_amdgcn_sched_group_barrier(0x100, 1, 0);
             }
         }
-#else
-#pragma unroll
-        for (int ks = 0; ks < KS; ++ks) {
-            v4i bk[WI_ND];
-#pragma unroll
-            for (int d = 0; d < WI_ND; ++d) bk[d] = bj[(d * KS + ks) * 64];
-            // h x digit d: weight 256^(7 - d); l' x digit d: 256^(6 - d) (the l' chain second, so
-            // the two MFMAs into one accumulator are 7 apart)
-#pragma unroll
-            for (int d = 0; d < WI_ND; ++d) acc[7 - d] = WI_MFMA(ah[ks], bk[d], acc[7 - d]);
-#pragma unroll
-            for (int d = 0; d < WI_ND; ++d) acc[6 - d] = WI_MFMA(al[ks], bk[d], acc[6 - d]);
-        }
-#endif
     };
     // tile j's powers from its accumulators into the wave's scratch pw
     auto epa = [&](const v4i(&acc)[WI_NW], int j) __attribute__((always_inline)) {
@@ -559,17 +483,6 @@ __global__ __launch_bounds__(256) void welch_i8_bands_kernel(const int64_t *__re
     }
 }
 
-// one balanced base-256 digit expansion of T: T = sum_b d[b] 256^(6 - b); false if T needs more
-bool balanced_digits7(int64_t T, int8_t (&d)[WI_ND]) {
-    for (int b = WI_ND - 1; b >= 0; --b) {
-        int64_t r = ((T % 256) + 256) % 256;
-        if (r >= 128) r -= 256;
-        d[b] = (int8_t)r;
-        T = (T - r) / 256;
-    }
-    return T == 0;
-}
-
 }  // namespace
 
 // the int8 path applies: int16 samples (checked at launch), nperseg a multiple of 64 up to 512, at
@@ -578,27 +491,6 @@ bool welch_i8_shape(const msd_welch_cfg &c, int nseg, int nslots, const double *
     if (c.nperseg % 64 != 0 || c.nperseg > 64 * WI_MAXKS || nseg < 1 || nseg > 16 || nslots < 1) return false;
     for (int n = 0; n < c.nperseg; ++n)
         if (!std::isfinite(window[n]) || std::fabs(window[n]) > 1.0) return false;
-    return true;
-}
-
-// T_n = round(v_n 2^53) with sum_n T_n = 0 exactly: floors, then the largest remainders rounded up
-// (sum_n v_n = 0 up to long double rounding, so the count to round up lies in [0, L)); |T_n - v_n 2^53| < 1
-bool zero_sum_round(const std::vector<long double> &v, std::vector<int64_t> &T) {
-    const int L = (int)v.size();
-    std::vector<long double> frac(L);
-    std::vector<int> idx(L);
-    int64_t S = 0;
-    for (int n = 0; n < L; ++n) {
-        const long double s = v[n] * 0x1p53L, f = floorl(s);
-        T[n] = (int64_t)f;
-        frac[n] = s - f;
-        S += T[n];
-        idx[n] = n;
-    }
-    const int64_t R = -S;
-    if (R < 0 || R > L) return false;
-    std::stable_sort(idx.begin(), idx.end(), [&](int a, int b) { return frac[a] > frac[b]; });
-    for (int64_t r = 0; r < R; ++r) T[idx[r]] += 1;
     return true;
 }
 
@@ -645,7 +537,7 @@ int welch_i8_build(msd_welch_plan *p, const double *window) {
         if (!zero_sum_round(cv, T)) return fail(MSD_ERR_INVALID, "welch_i8: coefficient rounding");
         for (int n = 0; n < L; ++n) {
             int8_t d[WI_ND];
-            if (!balanced_digits7(T[n], d)) return fail(MSD_ERR_INVALID, "welch_i8: coefficient beyond 7 digits");
+            if (!balanced_digits(T[n], d)) return fail(MSD_ERR_INVALID, "welch_i8: coefficient beyond 7 digits");
             for (int b = 0; b < WI_ND; ++b) dig[(size_t)b * L + n] = d[b];
         }
         // |acc_w| <= 128 (sum_n |d_(7-w)n| + sum_n |d_(6-w)n|) (h x digit 7 - w, l' x digit 6 - w;
@@ -663,7 +555,7 @@ int welch_i8_build(msd_welch_plan *p, const double *window) {
             for (int ks = 0; ks < KS; ++ks)
                 for (int grp = 0; grp < 4; ++grp)
                     for (int jj = 0; jj < 16; ++jj) {
-                        const int n = 64 * ks + (jj < 8 ? 8 * grp + jj : 32 + 8 * grp + (jj - 8));
+                        const int n = frag_sample(ks, grp, jj);
                         const int lane = grp * 16 + cc;
                         frag[((((size_t)ct * WI_ND + b) * KS + ks) * 64 + lane) * 16 + jj] = dig[(size_t)b * L + n];
                     }
@@ -676,11 +568,7 @@ int welch_i8_build(msd_welch_plan *p, const double *window) {
     if (e == hipSuccess) e = hipMemcpy(base + nb_frag, dbl.data(), nb_dbl, hipMemcpyHostToDevice);
     if (e != hipSuccess) return hip_fail(e, "welch plan: int8 tables");
     p->i8_nct = nct;
-#ifdef WI_FORCE_NOPAIRS
-    pairs = false;  // (A/B build)
-#endif
-    p->i8_pairs = pairs && !std::getenv("MSD_WELCH_I8_NOPAIRS");
-    p->i8_special = WI_SPECIAL && !std::getenv("MSD_WELCH_I8_GENERIC");  // (A/B and the identity test)
+    p->i8_pairs = pairs;
     return MSD_OK;
 }
 
@@ -723,7 +611,8 @@ int launch_welch_i8(msd_welch_plan *p, const int16_t *x, const int64_t *off, con
     const double folded = c.scale * A.xscale * A.xscale;
     A.fold = pow2 && std::isnormal(folded) && std::isnormal(A.xscale * A.xscale);
     A.pscale = A.fold ? folded : c.scale;
-    A.pairs = p->i8_pairs;
+    const int form = p->ctx->welch_i8_form;  // MSD_OPT_WELCH_I8_FORM (test hook)
+    A.pairs = p->i8_pairs && !(form & 1);
     A.rnseg = 1.0 / (double)A.nseg;
     const size_t lds = (size_t)A.cg * per_ct + scratch;
     const v4i *frag = static_cast<const v4i *>(p->d_i8);
@@ -747,7 +636,7 @@ int launch_welch_i8(msd_welch_plan *p, const int16_t *x, const int64_t *off, con
         WI_CASE(2)
         WI_CASE(3)
         case 4:  // the live default (nperseg 256, 5 segments of a 0.2 s block at 4 kHz): its own instantiation
-            if (A.nseg == 5 && A.fold && p->i8_special) WI_LAUNCH(4, 5);
+            if (A.nseg == 5 && A.fold && !(form & 2)) WI_LAUNCH(4, 5);
             else WI_LAUNCH(4, 0);
             break;
         WI_CASE(8)

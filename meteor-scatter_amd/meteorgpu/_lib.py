@@ -45,6 +45,8 @@ OPT_CSTFT_SCHED = 6
 OPT_STFT_SCHED = 7
 OPT_BLOCK_GOERTZEL = 8
 OPT_WELCH_GOERTZEL = 9
+OPT_WELCH_I8_FORM = 10     # test hook: bit 0 no int32 pairs, bit 1 the generic instantiation
+OPT_STREAM_EPS_LOG2 = 11   # test hook: the stream detector's near-tie bound times 2^n
 COMM_ID_BYTES = 128
 
 

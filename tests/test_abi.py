@@ -31,6 +31,13 @@ def test_binding_matches_header():
     assert sorted(_lib.SYMBOLS) == _declared()
 
 
+def test_binding_options_match_header():
+    src = open(os.path.join(ROOT, "include", "msdsp.h")).read()
+    opts = {name: int(v) for name, v in re.findall(r"^#define MSD_(OPT_[A-Z0-9_]+)\s+(\d+)\s*$", src, flags=re.M)}
+    assert len(opts) >= 11 and "OPT_WELCH_I8_FORM" in opts and "OPT_STREAM_EPS_LOG2" in opts
+    assert {n: getattr(_lib, n, None) for n in opts} == opts
+
+
 def test_abi_version_and_error_string():
     lib = _lib.load()
     assert lib.msd_abi_version() == 1

@@ -87,3 +87,15 @@ def test_c5_spectrogram_spill_bounded(audit):
     c5 = {k: r for k, r in audit.items() if "cstft4096_kernel" in k}
     assert c5
     assert max(r["private_segment_fixed_size"] for r in c5.values()) <= 96
+
+
+def test_library_reads_no_environment():
+    # which kernel or schedule runs is chosen by msd_set_option alone (include/msdsp.h): the library
+    # imports neither getenv nor the sscanf that parsed the round-5 / round-6 A/B variables
+    import subprocess
+    txt = subprocess.run([f"{kr.LLVM}/llvm-readelf", "--dyn-syms", "-W", SO], capture_output=True, text=True,
+                         check=True).stdout
+    undefined = [ln.split()[-1] for ln in txt.splitlines() if " UND " in ln]
+    assert len(undefined) > 20, "expected the library's imports"
+    bad = [s for s in undefined if s.split("@")[0] in ("getenv", "secure_getenv", "__isoc99_sscanf", "sscanf")]
+    assert not bad, bad

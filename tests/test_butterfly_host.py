@@ -1,7 +1,9 @@
-"""The STFT kernels' DFT8 butterflies (csrc/fft_butterfly.h, the header stft1024.hip compiles) on the
-CPU: `make -C meteor-scatter_amd/csrc butterfly` builds csrc/butterfly_check.cpp with
-g++ -fsanitize=address,undefined, and the program compares dft8 and dft8_windowed with a long-double
-8-point DFT on 10 000 random inputs and the unit vectors (4 float ulp of the input norm per output).
+"""The STFT kernels' butterflies (csrc/fft_butterfly.h, the header stft.hip, stft1024.hip and
+cstft.hip compile) on the CPU: `make -C meteor-scatter_amd/csrc butterfly` builds
+csrc/butterfly_check.cpp with g++ -fsanitize=address,undefined, and the program compares dft8 and
+dft8_windowed with a long-double 8-point DFT on 10 000 random inputs and the unit vectors (4 float ulp
+of the input norm per output), dft4 and dft16 with the 4- and 16-point DFT (2 and 14 ulp, the bounds
+its header derives from their roundings).
 A sanitizer report aborts the program (-fno-sanitize-recover=all), which fails the test."""
 import os
 import shutil
@@ -26,4 +28,6 @@ def test_dft8_against_long_double():
     r = subprocess.run([EXE, "10000", "1"], capture_output=True, text=True, timeout=120, env=env)
     assert r.returncode == 0, f"{r.stdout}\n{r.stderr[-4000:]}"
     assert "ERROR: AddressSanitizer" not in r.stderr and "runtime error" not in r.stderr, r.stderr[-4000:]
-    assert r.stdout.startswith("ok 10000 random + 16 unit inputs"), r.stdout
+    lines = r.stdout.splitlines()
+    assert len(lines) == 2 and lines[0].startswith("ok 10000 random + 16 unit inputs"), r.stdout
+    assert lines[1].startswith("ok 10000 random + 32 unit inputs: worst error dft4") and "dft16" in lines[1], r.stdout

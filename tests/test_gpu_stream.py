@@ -422,9 +422,10 @@ def test_iq_chunked_spectrogram_matches_whole():
     assert np.array_equal(np.asarray(t1), np.asarray(t2), equal_nan=True)
 
 
-def _random_case(seed, thresholds=True):
+def _random_case(seed, thresholds=True, eps_log2=0):
     """seeded random settings, segment lengths and shard cuts through the device plans (one
-    context per rank-thread): bit-exact with the one-process oracle"""
+    context per rank-thread, its MSD_OPT_STREAM_EPS_LOG2 set to eps_log2): bit-exact with the
+    one-process oracle"""
     from meteorgpu import _lib, stream
     rng = np.random.default_rng(7000 + seed)
     n = int(rng.integers(2000, 40000))
@@ -444,6 +445,7 @@ def _random_case(seed, thresholds=True):
         lo, hi = shard_bounds(n, world, r, cuts)
         ctx = _lib.Context(0)
         try:
+            ctx.set_option(_lib.OPT_STREAM_EPS_LOG2, eps_log2)
             cfg = _lib.det_cfg(adaptive, k, W, 0, Fa, F0)
             plan = _lib.StreamPlan(ctx, cfg, n, lo, hi - lo, seg_len=seg, head_frames=16384)
             plan.set_delta(d[lo:hi])
@@ -481,11 +483,10 @@ def test_random_sharded_decisions_only(seed):
 
 
 @pytest.mark.parametrize("seed", [1, 5])
-def test_decisions_only_wide_bound(seed, monkeypatch):
-    """the bound widened (MSD_STREAM_EPS_SCALE) until every unfrozen frame is a near tie: the
-    per-frame exact path carries the whole detector"""
-    monkeypatch.setenv("MSD_STREAM_EPS_SCALE", "1e30")
-    _random_case(seed, thresholds=False)
+def test_decisions_only_wide_bound(seed):
+    """the bound widened (MSD_OPT_STREAM_EPS_LOG2 = 100: 2^100 > 1e30) until every unfrozen frame is a
+    near tie: the per-frame exact path carries the whole detector"""
+    _random_case(seed, thresholds=False, eps_log2=100)
 
 
 def test_decisions_only_exact_ties():

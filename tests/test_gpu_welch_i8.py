@@ -139,15 +139,19 @@ def _plan_cfg(live, fs, bs, nfft, f0, width, nperseg):
     return c, win
 
 
-def _run(c, win, x, goertzel):
+def _run(c, win, x, goertzel, form=0, ctx=None):
+    """form: MSD_OPT_WELCH_I8_FORM for the run (bit 0 the eight-term digit sum, bit 1 the generic
+    instantiation), set on the existing plan's context and restored"""
     from meteorgpu import _lib, dsp
-    ctx = dsp.context(0)
+    ctx = dsp.context(0) if ctx is None else ctx
     plan = _lib.WelchPlan(ctx, c, win)
     ctx.set_option(_lib.OPT_WELCH_GOERTZEL, int(goertzel))
     try:
+        ctx.set_option(_lib.OPT_WELCH_I8_FORM, form)
         return plan.run(np.ascontiguousarray(x))
     finally:
         ctx.set_option(_lib.OPT_WELCH_GOERTZEL, 0)
+        ctx.set_option(_lib.OPT_WELCH_I8_FORM, 0)
         plan.close()
 
 
@@ -262,7 +266,7 @@ def test_welch_i8_ragged_batch_and_psd(live):
 
 
 @pytest.mark.gpu
-def test_welch_i8_pairs_bit_identical(live, monkeypatch):
+def test_welch_i8_pairs_bit_identical(live):
     """the int32-pair digit combination (the default plan's) and the eight-term one give the same
     float64 values: both round the exact digit sum once; so do the live default's own instantiation
     (5 segments, folded scale) and the generic one"""
@@ -272,13 +276,42 @@ def test_welch_i8_pairs_bit_identical(live, monkeypatch):
     x = _stress(x, fs)
     c, win = _plan_cfg(live, fs, 0.2, 4096, 1000, 100, 256)
     got = _run(c, win, x, False)
-    monkeypatch.setenv("MSD_WELCH_I8_NOPAIRS", "1")
-    ref = _run(c, win, x, False)
+    ref = _run(c, win, x, False, form=1)
     assert np.array_equal(got, ref)
     # and the generic instantiation (runtime segment count) against the live default's own
-    monkeypatch.setenv("MSD_WELCH_I8_GENERIC", "1")
-    assert np.array_equal(_run(c, win, x, False), ref)
+    assert np.array_equal(_run(c, win, x, False, form=3), ref)
     np.testing.assert_allclose(got[np.isfinite(got)], _scipy_band_db(x, fs, c)[np.isfinite(got)], rtol=0, atol=1e-9)
+
+
+@pytest.mark.gpu
+def test_test_hook_options_per_context(live):
+    """MSD_OPT_WELCH_I8_FORM and MSD_OPT_STREAM_EPS_LOG2 refuse values outside 0..3 / 0..1023, and
+    hold for their own context only: while one context runs form 3, a context created beside it runs
+    the default form -- every form bit-identical, so all three outputs are equal"""
+    from meteorgpu import _lib, dsp, synth
+    ctx = dsp.context(0)
+    for opt, top in ((_lib.OPT_WELCH_I8_FORM, 3), (_lib.OPT_STREAM_EPS_LOG2, 1023)):
+        for bad in (-1, top + 1):
+            with pytest.raises(_lib.MsdError) as e:
+                ctx.set_option(opt, bad)
+            assert e.value.code == _lib.MSD_ERR_INVALID
+        ctx.set_option(opt, top)
+        ctx.set_option(opt, 0)
+    fs = 4000
+    x, _ = synth.synth_real(seed=78, fs=fs, duration_s=1.0, f0=1000, sigma=400, rate_per_min=60)
+    c, win = _plan_cfg(live, fs, 0.2, 4096, 1000, 100, 256)
+    base = _run(c, win, x, False)
+    other = _lib.Context(0)
+    plan = _lib.WelchPlan(ctx, c, win)
+    try:
+        ctx.set_option(_lib.OPT_WELCH_I8_FORM, 3)
+        second = _run(c, win, x, False, ctx=other)  # created and run while ctx holds form 3
+        first = plan.run(np.ascontiguousarray(x))
+    finally:
+        ctx.set_option(_lib.OPT_WELCH_I8_FORM, 0)
+        plan.close()
+        other.close()
+    assert np.array_equal(first, second) and np.array_equal(first, base)
 
 
 @pytest.mark.gpu

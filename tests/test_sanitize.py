@@ -7,7 +7,8 @@ files or plans device work, built with g++ -fsanitize=address,undefined
   same samples; libmsdsp's own reader (msd_wav_probe / msd_wav_read, the same wav_parse.h) agrees;
 * a seeded fuzz of mutated / truncated WAV images decoded in memory (exact-size buffers: any read
   past the image is an AddressSanitizer report), numpy's np.sum leaf programs and the float64
-  refinement planner.
+  refinement planner;
+* the int8-MFMA kernels' coefficient digits and fragment order (i8_digits.h).
 
 A sanitizer report aborts the harness (-fno-sanitize-recover=all), which fails the test."""
 import os
@@ -176,3 +177,12 @@ def test_refine_plan_under_sanitizers(harness):
     assert run(harness, "refine", 4096, 1024, 21, 5000, -65, -63, 10 ** 6, 0, 10).startswith("err")
     assert run(harness, "refine", 4096, 1024, 21, 22, -65, -63, 8192, 0, 10).startswith("err")
     assert run(harness, "refine", 131072, 1024, 21, 22, -65, -63, 10 ** 7, 0, 10).startswith("err")  # > 65536
+
+
+@pytest.mark.parametrize("seed", [1, 2])
+def test_i8_digits_under_sanitizers(harness, seed):
+    # i8_digits.h, the host half of the three int8-MFMA kernels' exactness argument: balanced_digits<6>
+    # and <7> reproduce T or refuse it exactly when it does not fit, zero_sum_round's integers sum to 0
+    # within 1 of the scaled coefficients, frag_sample maps a K step's fragment bytes onto its samples
+    out = run(harness, "i8", seed, 200000)
+    assert out.startswith("ok") and out.split()[3] == "200000", out
