@@ -2,23 +2,29 @@
 // configuration: scipy.signal.spectrogram(x, fs, 'hann', 1024, 512) as called at
 // dsp/src/main.py:52-54 / :132-133 and BASELINE configs C1-C4).
 //
-// Mapping.  A wave transforms two frames at once (two independent
-// instruction streams, interleaved by the compiler), 64 lanes x 8 complex points
-// per frame, every radix-8 Stockham pass in registers:
+// Mapping (measured in profiles/stft1024_xwave_ab.txt: 5.564 against 5.713 ms per C3 launch for the
+// mapping before it, in which a wave kept its two frames through pass 3 and the powers left through an
+// LDS tile; LDS issue cycles -19 %, VALU instructions -3.7 %, no bank conflicts).  One workgroup = 16 waves (4 per SIMD: one wave alone issues a VALU op
+// only every ~4 cycles, so the SIMD needs several) = one tile of 32 consecutive frames.  Every
+// radix-8 Stockham pass runs in registers, 8 complex points per lane and stream, two independent
+// instruction streams per wave (interleaved by the compiler):
+//   passes 1 and 2 by frame: wave w owns the frame pair (2w, 2w + 1) of the tile, one frame per stream,
+//   64 lanes x 8 points;
 //   load    lane l holds z[l + 64 r] = x[2(l+64r)] + i x[2(l+64r)+1] (r = 0..7): one
 //           sample pair per lane per instruction, 256 B coalesced per wave;
 //   detrend frame mean from an exact integer reduction: DPP adds inside each row of
 //           16 lanes, then four v_readlane (no LDS round trip);
-//   pass 1  → LDS transpose → pass 2 → LDS transpose → pass 3: lane l computes the
-//           pass-3 butterfly pi(l) (a table: conjugate pairs j, 64-j in adjacent lanes,
-//           pi(0)=0, pi(1)=32), so it holds Z[pi(l) + 64 r] and the conjugate partner
-//           Z[512 - k] lives in lane l^1 (one DPP quad_perm per value);
-//   post    real-spectrum split, |X|^2 * scale (x2 off DC / Nyquist) → LDS tile
-//           [513][32] (row pitch 34, tile_at()).
-// One workgroup = 16 waves (4 per SIMD: one wave alone issues a VALU op only every
-// ~4 cycles, so the SIMD needs several) = one tile of 32 consecutive frames, one
-// frame pair per wave.  The tile leaves as 128-B row segments.  Workgroups are
-// persistent and walk a contiguous range of tiles (the half frame shared by
+//   pass 1  → transpose through the frame's LDS region → pass 2 → the frame's LDS region;
+//   pass 3 by bin, across the workgroup: the 64 pass-3 butterflies are 32 slots, the conjugate pairs
+//           (j, 64 - j), j = 1..31, and the self-conjugate (0, 32); a half-wave owns one slot and its 32
+//           lanes are the tile's 32 frames.  Stream A is butterfly j, stream B butterfly 64 - j, so a
+//           lane holds Z[j + 64 r] and its conjugate partner Z[512 - j - 64 r] (B's register 7 - r) of
+//           its own frame: no cross-lane traffic.  B's twiddles are the conjugates of A's, its DFT8
+//           outputs A's formula shifted by one index (W512^((64-j) r) = W8^r conj(W512^(j r)));
+//   post    real-spectrum split, |X|^2 * scale (x2 off DC / Nyquist): a lane holds one column entry
+//           of 16 rows (17 in slot 0), and each row leaves as one non-temporal dword store in
+//           which each half-wave writes one 128-B row segment, straight from registers.
+// Workgroups are persistent and walk a contiguous range of tiles (the half frame shared by
 // neighbouring tiles is re-read from L2); each wave loads its next tile's frame pair
 // into the sample registers as soon as the current pair is windowed.
 #include <vector>
@@ -32,55 +38,49 @@
 namespace msd {
 namespace {
 
-// The previous tile's write-out (row groups j = 0..4, rows 128 j + tid / 8) leaves in two bursts:
-// groups [0, F_WO_SPLIT) after the first transposes, [F_WO_SPLIT, 5) after the second ones (the
-// placement measured fastest among 13; the A/B variants live in tools/)
-constexpr int F_WO_SPLIT = 2;
 constexpr int F_NW = 16;                  // waves per workgroup (4 per SIMD)
 constexpr int F_TT = 32;                  // frames per tile
 constexpr int F_K = 513;                  // one-sided bins
-constexpr int F_PITCH = F_TT + 2;         // tile row pitch (floats)
-constexpr int F_SCRF = 576;               // float2 per frame scratch (phys(511) = 571)
-constexpr int F_TILE_BYTES = ((F_K * F_PITCH * 4 + 15) / 16) * 16;
-constexpr int F_SCR_OFF = F_TILE_BYTES;
-constexpr int F_TAB_OFF = F_SCR_OFF + F_NW * F_SCRF * 8;
-// per-lane constants, one 208-B row per lane [lane][26 float2]: window pairs w[2(l + 64 r)..] (r = 0..7,
-// at 0), post twiddles W1024^{pi(l) + 64 r} (r = 0..3, at 8), pass-2 twiddles W64^{(l&7) r} (r = 1..7,
-// at 12) and pass-3 twiddles W512^{pi(l) r} (r = 1..7, at 19).  Read as ds_read_b128 (4 LDS cycles
-// per KB, the ds_read_b64 rate; the [r][lane] layout's reads were paired into ds_read2st64_b64 at
-// 8 cycles per KB); the 52-dword row stride is 4 x odd, so a b128 lane group hits 16 disjoint
-// 4-bank ranges (conflict-free)
-constexpr int F_TABW = 26;
-constexpr int F_LDS = F_TAB_OFF + F_TABW * 64 * 8;
+constexpr int F_SCRF = 576;               // float2 per frame region (phys(511) = 571)
+// Frame buffer: one region per frame of the tile.  Frame f sits at (f >> 1) * F_PAIRF + (f & 1) * F_SCRF
+// and holds point n at phys(n) ^ (f & 1).  In the pass-3 reads the 32 lanes of a ds_read_b64 group read
+// the same point of the 32 frames: with F_PAIRF = 2 (mod 32) the pair bases take the 16 even float2
+// banks and the parity flip the odd ones, so the group covers all 64 banks once.  Every base stays
+// 16-B aligned for the pass-1 ds_write_b128 (an odd frame swaps the two float2 of a write instead),
+// and inside a frame the flip only permutes banks, so the phys() patterns stay conflict-free
+// (tools/lds_bank_model.py checks every access pattern of the kernel).
+constexpr int F_PAIRF = 2 * F_SCRF + 2;
+constexpr int F_TAB_OFF = (F_TT / 2) * F_PAIRF * 8;
+// per-lane constants, one 144-B row per lane [lane][18 float2]: window pairs w[2(l + 64 r)..] (r = 0..7,
+// at 0) and pass-2 twiddles W64^{(l&7) r} (r = 1..7, at 8).  Read as ds_read_b128; the 36-dword row
+// stride is 4 x odd, so a b128 lane group hits 16 disjoint 4-bank ranges (conflict-free)
+constexpr int F_TABW = 18;
+// per-slot constants, one 96-B row per slot [33][12 float2]: pass-3 twiddles W512^{j r} (r = 1..7, at 0)
+// and post twiddles W1024^{j + 64 r} (r = 0..3, at 8; those of r + 4 are -i times these).  Row 32 is
+// butterfly 32 of slot 0 (its post twiddles times i, so that the r >= 4 form applies).  A half-wave
+// reads one address (broadcast)
+constexpr int F_SLOT_OFF = F_TAB_OFF + F_TABW * 64 * 8;
+constexpr int F_SLOTW = 12;
+// integer samples: the frames' mean remainders, double-buffered by tile parity (written by the frame's
+// wave before the pass-2 barrier, read by wave 0 in the post pass)
+constexpr int F_RB_OFF = F_SLOT_OFF + 33 * F_SLOTW * 8;
+constexpr int F_LDS = F_RB_OFF + 2 * F_TT * 4;
 static_assert(F_LDS <= 160 * 1024, "LDS budget");
+static_assert(F_PAIRF % 32 == 2 && F_TAB_OFF % 16 == 0 && F_SLOT_OFF % 16 == 0, "frame buffer banking / alignment");
 
 // cadd / csub / cmul / mul_mi, dft4, dft8, dft8_windowed (host-checkable: butterfly_check.cpp)
 using namespace bfly;
 
-// Transpose-scratch layout (float2 index): bit 4 of n flips bits 1 and 3, plus 4 float2 of
-// padding per 32.  Together with the pass-3 lane table below it makes all four transpose
-// access patterns (16-B pass-1 writes, 8-B reads, 8-B pass-2 writes, pass-3 reads) free of
-// bank conflicts under the gfx950 LDS model — found by tools/lds_swizzle_search.py.
+// a * conj(b)
+__device__ __forceinline__ float2 cmulc(float2 a, float2 b) {
+    return make_float2(a.x * b.x + a.y * b.y, a.y * b.x - a.x * b.y);
+}
+
+// Frame-region layout (float2 index): bit 4 of n flips bits 1 and 3, plus 4 float2 of
+// padding per 32.  It makes the transposes' access patterns inside a frame (16-B pass-1 writes, 8-B
+// reads, 8-B pass-2 writes) free of bank conflicts under the gfx950 LDS model — found by
+// tools/lds_swizzle_search.py.  phys(n + 64 r) = phys(n) + 72 r.
 __device__ __forceinline__ int phys(int n) { return (n ^ (((n >> 4) & 1) * 10)) + ((n >> 5) << 2); }
-
-// pass-3 butterfly of each lane: conjugate pairs (j, 64-j) in adjacent lanes, (0, 32) in
-// lanes 0/1, grouped so that the pass-3 reads are conflict-free (tools/lds_swizzle_search.py)
-__constant__ int8_t k_pass3_lane[64] = {0,  32, 1,  63, 3,  61, 5,  59, 6,  58, 7,  57, 12, 52, 14, 50,
-                                        13, 51, 15, 49, 16, 48, 18, 46, 25, 39, 26, 38, 27, 37, 28, 36,
-                                        2,  62, 4,  60, 8,  56, 9,  55, 10, 54, 11, 53, 17, 47, 19, 45,
-                                        20, 44, 21, 43, 22, 42, 23, 41, 24, 40, 29, 35, 30, 34, 31, 33};
-
-// Output tile: bin k, frame column c at k * 34 + ((c + rot(k)) & 31) (pitch 34 keeps rows 8-B
-// aligned; an XOR-swizzled pitch-32 tile read by conflict-free ds_read_b128 measured 1.5 % slower).
-// The half-row rotation of rows k = 32, 40, 48, 56 (mod 64) makes the post pass's tile writes
-// conflict-free: a 16-lane ds_write_b64 group holds 8 conjugate pairs (j, 64 - j) of butterflies,
-// whose rows 2k mod 32 banks cover 15 residues k mod 16 with one doubled (0 or 8, the pair
-// j = 0 / 32, 16 / 48, 8 / 56 or 24 / 40), a 2-way conflict in every group (SQ_LDS_BANK_CONFLICT
-// 1.30e8 = 32 cycles per wave-iteration, all of the kernel's); moving one row of each such pair
-// by 16 banks fills the missing residue.  The write-out's rows 2m, 2m + 1 keep complementary
-// banks (tools/lds_bank_model.py checks every access pattern of the kernel).
-__device__ __forceinline__ int tile_rot(int k) { return (k & 39) == 32 ? 16 : 0; }
-__device__ __forceinline__ int tile_at(int k, int c) { return k * F_PITCH + ((c + tile_rot(k)) & 31); }
 
 template <typename T>
 struct PairIO;
@@ -161,21 +161,6 @@ __device__ __forceinline__ void load_pair(const T *__restrict__ x, const FileCur
     }
 }
 
-// lanes 0 and 1 take their post-pass partner value from their own registers (a0 / a1 for lane 0,
-// b0 / b1 for lane 1) instead of the DPP one: two exec-masked moves (full-rate v_mov_b32) instead
-// of two v_cndmask_b32 selects (quarter-rate) per value.  The wave is fully active here.
-__device__ __forceinline__ void lane01_fix(float &m0, float &m1, float &m2, float &m3, float a0, float a1, float a2,
-                                           float a3, float b0, float b1, float b2, float b3) {
-    asm volatile(
-        "s_mov_b64 exec, 1\n\t"
-        "v_mov_b32 %0, %4\n\tv_mov_b32 %1, %5\n\tv_mov_b32 %2, %6\n\tv_mov_b32 %3, %7\n\t"
-        "s_mov_b64 exec, 2\n\t"
-        "v_mov_b32 %0, %8\n\tv_mov_b32 %1, %9\n\tv_mov_b32 %2, %10\n\tv_mov_b32 %3, %11\n\t"
-        "s_mov_b64 exec, -1"
-        : "+v"(m0), "+v"(m1), "+v"(m2), "+v"(m3)
-        : "v"(a0), "v"(a1), "v"(a2), "v"(a3), "v"(b0), "v"(b1), "v"(b2), "v"(b3));
-}
-
 // WIDE: 64-bit output offsets (files of 2^20 frames and more); SH: hop 512 with integer samples
 // DYN: the workgroups take chunks of consecutive tiles from a guided schedule (sched[k] .. sched[k+1],
 // at least 2 tiles) by an atomic ticket instead of one fixed range each (as cstft4096_kernel, where it
@@ -191,36 +176,76 @@ __global__ __launch_bounds__(F_NW * 64, 1) void stft1024_kernel(
     using IO = PairIO<T>;
     using raw_t = typename IO::raw_t;
     extern __shared__ __attribute__((aligned(16))) char smem[];
-    float *tile = reinterpret_cast<float *>(smem);
+    float2 *buf = reinterpret_cast<float2 *>(smem);
     const int tid = threadIdx.x;
     const int l = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);  // wave-uniform: scalar frame addresses
-    float2 *scr = reinterpret_cast<float2 *>(smem + F_SCR_OFF) + wave * F_SCRF;
+    // passes 1 and 2: the regions of this wave's frames 2 wave (even) and 2 wave + 1 (odd)
+    float2 *fb0 = buf + wave * F_PAIRF, *fb1 = fb0 + F_SCRF;
     float2 *t_all = reinterpret_cast<float2 *>(smem + F_TAB_OFF);
+    float2 *s_all = reinterpret_cast<float2 *>(smem + F_SLOT_OFF);
+    float *rbuf = reinterpret_cast<float *>(smem + F_RB_OFF);
     const float2 *tab = t_all + l * F_TABW;  // this lane's constants
-    auto pi_of = [](int i) { return (int)k_pass3_lane[i]; };
     for (int i = tid; i < 64 * F_TABW; i += F_NW * 64) {
         const int li = i / F_TABW, c = i % F_TABW;
-        float2 e;
+        float2 e = make_float2(0.f, 0.f);
         if (c < 8) {
             const float2 gw = *reinterpret_cast<const float2 *>(g_win + 2 * (li + 64 * c));
             e = make_float2(gw.x * wscale, gw.y * wscale);  // window * sqrt(scale / 2)
-        } else if (c < 12) {
-            e = g_post[pi_of(li) + 64 * (c - 8)];
-        } else if (c < 19) {
-            e = g_tw[8 * (li & 7) * (c - 11)];
-        } else {
-            e = g_tw[pi_of(li) * (c - 18)];
+        } else if (c < 15) {
+            e = g_tw[8 * (li & 7) * (c - 7)];
         }
         t_all[i] = e;
     }
-    // the table entries as ds_read_b128 (two float2 each) / ds_read_b64
+    for (int i = tid; i < 33 * F_SLOTW; i += F_NW * 64) {
+        const int j = i / F_SLOTW, c = i % F_SLOTW;  // row 32: butterfly 32
+        float2 e = make_float2(0.f, 0.f);
+        if (c < 7) {
+            e = g_tw[j * (c + 1)];
+        } else if (c >= 8) {
+            e = g_post[j + 64 * (c - 8)];
+            if (j == 32) e = make_float2(-e.y, e.x);  // times i
+        }
+        s_all[i] = e;
+    }
+    // Transpose addresses as lane bases plus compile-time offsets (LDS instruction immediates), q = 1 the
+    // odd frame's (^ 1).  Pass-1 writes phys(8 l + r): bit 4 of 8 l + r is a lane bit and flips r's bit 1,
+    // so r = 0, 4 go from wr0 and r = 2, 6 from wr2.  Pass-1 reads phys(l + 64 r) = phys(l) + 72 r.
+    // Pass-2 writes phys(o2 + 8 r): bit 4 is r's bit 1, which flips bit 1 of the lane part o2 (w2[q][1]) and
+    // bit 3 of 8 r; the padding is 8 (l >> 3) + 4 (r >> 2)
+    const int wr0 = phys(8 * l), wr2 = phys(8 * l + 2);
+    const int rd[2] = {phys(l), phys(l) ^ 1};
+    const int o2 = 64 * (l >> 3) + (l & 7), o2p = 8 * (l >> 3);  // pass 2 (Ns = 8): out[o2 + 8 r]
+    const int w2[2][2] = {{o2 + o2p, (o2 ^ 2) + o2p}, {(o2 ^ 1) + o2p, (o2 ^ 3) + o2p}};
+    auto c2 = [](int r) { return ((8 * r) ^ ((r & 2) ? 8 : 0)) + 4 * (r >> 2); };
+    // The transposes' reads, points n + 64 r (r = 0..7) at buf[idx + 72 r], as eight ds_read_b64 (2 LDS cycles
+    // each, one 32-lane group on banks mod 64 -- what the layouts are built for).  Off one base register the
+    // compiler merges pairs of them into ds_read2_b64 (8 cycles, 16-lane groups on banks mod 32), so r and
+    // r + 4 share a base (288 float2 apart: past a ds_read2's offsets) and the four bases are made opaque
+    auto read8 = [&](int idx, float2 (&dst)[8]) {
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+            int ik = idx + 72 * k;
+            asm volatile("" : "+v"(ik));
+            dst[k] = buf[ik];
+            dst[k + 4] = buf[ik + 288];
+        }
+    };
+    // the table entries as ds_read_b128 (two float2 each)
     auto tab4 = [&](int c) { return *reinterpret_cast<const float4 *>(tab + c); };
-    const int pi = pi_of(l);
-    // integer samples: the coefficient of the mean's fractional part b / 1024 at this lane's bin of
-    // register 0 -- 2 ws W_k / 1024 at k = 0 (lane pi = 0) and k = 1 (pi = 1), zero elsewhere
-    // (launch_fast_t: the window's DFT vanishes past bin 1)
-    const float2 dcw = pi == 0 ? dcw0 : (pi == 1 ? dcw1 : make_float2(0.f, 0.f));
+    // pass 3: this lane's frame of the tile and its half-wave's slot: butterflies jA (stream A) and jB
+    // (stream B); slot 0 is (0, 32), every other slot j the conjugate pair (j, 64 - j)
+    const int frm = l & 31, fpar = l & 1;
+    const int sl = 2 * wave + (l >> 5);
+    const int jB = sl ? 64 - sl : 32;
+    const int fbase = (frm >> 1) * F_PAIRF + fpar * F_SCRF;
+    const int i3a = fbase + (phys(sl) ^ fpar), i3b = fbase + (phys(jB) ^ fpar);
+    const float2 *stA = s_all + sl * F_SLOTW;
+    // output rows of this lane from the tile's base, as 32-bit byte offsets (WIDE = 0: K*ld*4 < 2^31) with
+    // the multiples of 64 rows as scalar offsets: bin j + 64 r at offA + 64 r rows, its mirror
+    // 512 - j - 64 r at offB + 64 (7 - r) rows
+    const uint32_t ld4 = (uint32_t)ld * 4u;
+    const uint32_t offA = (uint32_t)sl * ld4 + 4u * frm, offB = (uint32_t)(64 - sl) * ld4 + 4u * frm;
     __syncthreads();
 
     __shared__ int64_t slot[2];  // DYN: drawn chunk tickets
@@ -262,48 +287,8 @@ __global__ __launch_bounds__(F_NW * 64, 1) void stft1024_kernel(
     raw_t raw[NR];
     load_pair<T, SH>(x, cur, cur.ti * F_TT + wcol, hop, l, raw);
     bool b_ok = cur.ti * F_TT + wcol + 1 < cur.nfr;  // the pair's second frame exists (wave-uniform)
-    // 32-bit byte offsets of this thread's write-out rows k = 128 j + tid / 8 from the tile's base
-    uint32_t wo_off[5];
-#pragma unroll
-    for (int j = 0; j < 5; ++j)
-        wo_off[j] = (uint32_t)(128 * j + (tid >> 3)) * ((uint32_t)ld * 4u) + 16u * (uint32_t)(tid & 7);
-    // ---- tile → HBM: 513 rows x 32 floats (128 B), 8 lanes x 16 B per row.  Issued one
-    // iteration late (in the middle of the next tile's transform), so the stores drain while
-    // that tile computes; the next prefetch is issued before them, so the wait for it at the top
-    // of the loop never waits for a tile's stores.
-    auto write_out = [&](const FileCur &wc, auto j0c, auto j1c) {
-        constexpr int J0 = decltype(j0c)::value, J1 = decltype(j1c)::value;
-        // scalar base + lane offsets, 8 lanes x 16 B per row: two 8-B LDS reads → one 16-B
-        // store.  WIDE = 0: 32-bit offsets (K*ld*4 < 2^31, i.e. ld < 2^20 frames); WIDE = 1:
-        // 64-bit (longer files)
-        char *of = reinterpret_cast<char *>(out + wc.f * (int64_t)F_K * ld + wc.ti * F_TT);
-        const int qq = tid & 7;
-        const int rw = tile_rot(tid >> 3);  // = tile_rot(k) for every j (k = 128 j + tid / 8)
-        typedef float f4v __attribute__((ext_vector_type(4)));
-        // WIDE = 0: a buffer resource on the tile's base and the precomputed 32-bit row offsets (no
-        // per-store 64-bit address arithmetic)
-        const auto rsrc = __builtin_amdgcn_make_buffer_rsrc(of, 0, (int)((uint32_t)F_K * (uint32_t)ld * 4u), 0x00020000);
-#pragma unroll
-        for (int j = J0; j < J1; ++j) {
-            const int k = 128 * j + (tid >> 3);
-            if (k < F_K) {
-                const int c0 = k * F_PITCH + ((4 * qq + rw) & 31);  // tile_at(k, 4 qq); + 2: tile_at(k, 4 qq + 2)
-                const float2 a = *reinterpret_cast<const float2 *>(&tile[c0]);
-                const float2 b = *reinterpret_cast<const float2 *>(&tile[c0 + 2]);
-                const f4v v = f4v{a.x, a.y, b.x, b.y};
-                // streaming (non-temporal) stores: written once, never re-read here (A/B: -1 to -2 %)
-                if constexpr (WIDE)
-                    __builtin_nontemporal_store(v, reinterpret_cast<f4v *>(of + ((int64_t)k * ld * 4 + 16 * qq)));
-                else
-                    __builtin_amdgcn_raw_buffer_store_b128(v, rsrc, wo_off[j], 0, 2 /* nt */);
-            }
-        }
-    };
-    FileCur prev = cur;
-    // an int pinned in a scalar register at the loop end: as a loop-carried bool it lives as a lane mask,
-    // rebuilt by a select and a compare in every iteration (A/B: -0.4 to -0.7 %)
-    int have_prev = 0;
     const float hs = vgpr_f(0.70710678118654752440f);  // sqrt(1/2) of the DFT8s, in a VGPR
+    int tpar = 0;  // tile parity: the half of rbuf in use
 
     for (int64_t tl = tb;;) {
         // the next tile: the next of this range, else (DYN) the first of the next drawn chunk
@@ -399,37 +384,37 @@ __global__ __launch_bounds__(F_NW * 64, 1) void stft1024_kernel(
             b_ok = nxt.ti * F_TT + wcol + 1 < nxt.nfr;
         }
 
-        // ---- pass 1 (Ns = 1): out[8 l + r].  One scratch per wave: frame A's transpose is
-        // read back before frame B's is written (LDS executes a wave's accesses in order)
+        if constexpr (IO::kInt) {  // the frames' remainders to wave 0, which owns bins 0 and 1
+            if (l < 2) rbuf[tpar * F_TT + wcol + l] = l ? rb[1] : rb[0];
+        }
+
+        // ---- pass 1 (Ns = 1): out[8 l + r], each frame through its own region (the odd frame's points
+        // at phys() ^ 1: the two float2 of a 16-B write swap)
         dft8_windowed(v[0], v[0], wv, hs);
         dft8_windowed(v[1], v[1], wv, hs);
 #pragma unroll
-        for (int q = 0; q < 2; ++q) {
-#pragma unroll
-            for (int r = 0; r < 8; r += 2)
-                *reinterpret_cast<float4 *>(&scr[phys(8 * l + r)]) =
-                    make_float4(v[q][r].x, v[q][r].y, v[q][r + 1].x, v[q][r + 1].y);
-            wave_sync();
-#pragma unroll
-            for (int r = 0; r < 8; ++r) v[q][r] = scr[phys(l + 64 * r)];
-            wave_sync();
+        for (int r = 0; r < 8; r += 2) {
+            const int n = ((r & 2) ? wr2 : wr0) + (r & 4);
+            *reinterpret_cast<float4 *>(&fb0[n]) =
+                make_float4(v[0][r].x, v[0][r].y, v[0][r + 1].x, v[0][r + 1].y);
+            *reinterpret_cast<float4 *>(&fb1[n]) =
+                make_float4(v[1][r + 1].x, v[1][r + 1].y, v[1][r].x, v[1][r].y);
         }
-        // the previous tile's write-out, split between here (after the first transposes) and after
-        // the second ones: its LDS reads and stores overlap the other waves' arithmetic in two
-        // smaller bursts instead of one (A/B: all at the loop top +2 %, all here 0, half here and
-        // half after the second transposes -3.4 %)
-        if (have_prev) write_out(prev, std::integral_constant<int, 0>{}, std::integral_constant<int, F_WO_SPLIT>{});
+        wave_sync();
+        read8(wave * F_PAIRF + rd[0], v[0]);
+        read8(wave * F_PAIRF + F_SCRF + rd[1], v[1]);
+        wave_sync();
         // ---- pass 2 (Ns = 8): out[64 (l>>3) + (l&7) + 8 r]
-        const int o2 = 64 * (l >> 3) + (l & 7);
-        float2 tw3_1;  // the first pass-3 twiddle shares the pass-2 table's last ds_read_b128
         {
-            float2 w[8];  // pass-2 twiddles r = 1..7 at 12..18
+            float2 w[8];  // pass-2 twiddles r = 1..7 at 8..14
 #pragma unroll
-            for (int r = 1; r < 8; r += 2) {
-                const float4 w4 = tab4(11 + r);
-                w[r] = make_float2(w4.x, w4.y);
-                if (r < 7) w[r + 1] = make_float2(w4.z, w4.w);
-                else tw3_1 = make_float2(w4.z, w4.w);
+            for (int r = 0; r < 8; r += 2) {
+                float4 w4 = tab4(8 + r);
+                w[r + 1] = make_float2(w4.x, w4.y);
+                if (r < 6) w[r + 2] = make_float2(w4.z, w4.w);
+                // the last entry's other half is padding: kept a 16-B read all the same (narrowed to a
+                // ds_read_b64, whose 32-lane groups meet the 36-dword lane stride in a 2-way conflict)
+                else asm volatile("" : "+v"(w4.z), "+v"(w4.w));
             }
 #pragma unroll
             for (int r = 1; r < 8; ++r) {
@@ -440,104 +425,141 @@ __global__ __launch_bounds__(F_NW * 64, 1) void stft1024_kernel(
         dft8(v[0], hs);
         dft8(v[1], hs);
 #pragma unroll
-        for (int q = 0; q < 2; ++q) {
-#pragma unroll
-            for (int r = 0; r < 8; ++r) scr[phys(o2 + 8 * r)] = v[q][r];
-            wave_sync();
-#pragma unroll
-            for (int r = 0; r < 8; ++r) v[q][r] = scr[phys(pi + 64 * r)];
-            wave_sync();
+        for (int r = 0; r < 8; ++r) {
+            fb0[w2[0][(r >> 1) & 1] + c2(r)] = v[0][r];
+            fb1[w2[1][(r >> 1) & 1] + c2(r)] = v[1][r];
         }
-        if (have_prev) write_out(prev, std::integral_constant<int, F_WO_SPLIT>{}, std::integral_constant<int, 5>{});
-        // ---- pass 3 (Ns = 64): butterfly pi(l) → lane holds Z[pi(l) + 64 r]
-        {
-            float2 w[8];  // pass-3 twiddles r = 1..7 at 19..25
-            w[1] = tw3_1;
-#pragma unroll
-            for (int r = 2; r < 8; r += 2) {
-                const float4 w4 = tab4(18 + r);
-                w[r] = make_float2(w4.x, w4.y);
-                w[r + 1] = make_float2(w4.z, w4.w);
-            }
-#pragma unroll
-            for (int r = 1; r < 8; ++r) {
-                v[0][r] = cmul(v[0][r], w[r]);
-                v[1][r] = cmul(v[1][r], w[r]);
-            }
-        }
-        dft8(v[0], hs);
-        dft8(v[1], hs);
+        lds_barrier();  // the tile's pass-2 output is complete
+        // ---- pass 3 (Ns = 64) by bin: this lane's frame frm, butterflies j (A) and 64 - j (B) of its
+        // half-wave's slot.  A holds Z[j + 64 r]; B's DFT8 input takes conj(A's twiddles) and its output
+        // index shifts by one: Z[64 - j + 64 k] = Y[(k + 1) & 7].
         // ---- post: X' = 2X = (Z + conj Zm) + W^k (-i)(Z - conj Zm), Zm = Z[(512 - k) mod 512],
-        // and from the same e, o the mirror bin X'[512 - k] = conj(e - W^k o).  Lane l owns the
-        // four pairs (k = pi(l) + 64 r, 512 - k), r = 0..3: Zm sits in lane l^1, register 7-r
-        // (one DPP quad_perm per value); lane 1 (k = 32 + 64 r): own register 7-r; lane 0
-        // (k = 64 r): own register (8-r)&7, its r = 0 pair being DC / Nyquist (no doubling), and
-        // it alone also owns the self-mirrored bin 256.  W^k from the LDS table.  The powers stay
-        // in registers until the tile is free (the previous tile's write-out has read it), so a
-        // wave's transform overlaps the other waves' write-out.
-        float pa[2][4], pb[2][4], p256[2];
-        // the window carries sqrt(scale / 2): |X'|^2 is the doubled one-sided density; lane 0's
-        // r = 0 pair (DC, Nyquist) is not doubled
-        const float sc0 = l == 0 ? 0.5f : 1.0f;
-        float2 wpost[4];  // post twiddles at 8..11: two ds_read_b128
+        // and from the same e, o the mirror bin X'[512 - k] = conj(e - W^k o).  The lane owns the
+        // eight pairs (k = j + 64 r, 512 - k), r = 0..7: Zm is B's register 7 - r = Y[(8 - r) & 7], and
+        // W^(k + 256) = -i W^k.  The window carries sqrt(scale / 2): |X'|^2 is the doubled one-sided density.
+        // SP (wave 0): its lanes 0..31 hold slot 0, butterflies 0 (A) and 32 (B, its own twiddle row), each
+        // its own conjugate partner: pairs r < 4 are (A[r], A[(8 - r) & 7]), bins 64 r and 512 - 64 r (r = 0:
+        // DC and Nyquist, not doubled), pairs r >= 4 are (B[r - 4], B[11 - r]), bins 32 + 64 (r - 4) and
+        // their mirrors, and bin 256 = 2 conj(Z[256]) is a 17th row.  Its lanes 32..63 hold slot 1;
+        // bins 0 and 1 take the integer mean's remainder (dcw0, dcw1).
+        char *of = reinterpret_cast<char *>(out + cur.f * (int64_t)F_K * ld + cur.ti * F_TT);
+        // WIDE = 0: a buffer resource on the tile's base, the lane's 32-bit row offsets and scalar
+        // multiples of 64 rows (no per-store 64-bit address arithmetic).  WIDE = 1: the lower of the two
+        // half-waves' rows as a 64-bit scalar base and one row (ld * 4 < 2^32 B) in the lane offset; rows that
+        // are not neighbours (slot 0's butterfly 32 beside slot 1) leave as one store per half-wave
+        const auto rsrc = __builtin_amdgcn_make_buffer_rsrc(of, 0, (int)((uint32_t)F_K * ld4), 0x00020000);
+        typedef __attribute__((address_space(1))) float gfloat;
+        // streaming (non-temporal) stores: written once, never re-read here.  row(h): the row of half-wave h
+        auto put = [&](float p, uint32_t voff, auto row, int srow, bool split = false) {
+            if constexpr (WIDE) {
+                if (split) {
 #pragma unroll
-        for (int r = 0; r < 4; r += 2) {
-            const float4 w4 = tab4(8 + r);
-            wpost[r] = make_float2(w4.x, w4.y);
-            wpost[r + 1] = make_float2(w4.z, w4.w);
-        }
+                    for (int h = 0; h < 2; ++h)
+                        if ((l >> 5) == h)
+                            __builtin_nontemporal_store(
+                                p, (gfloat *)(of + uniform_i64((int64_t)(row(h) + srow) * ld * 4)) + frm);
+                } else {
+                    const bool up = row(0) < row(1);  // rows of the two halves: neighbours
+                    const uint32_t o = ((l >> 5) == (up ? 1 : 0) ? ld4 : 0u) + 4u * frm;
+                    __builtin_nontemporal_store(
+                        p, (gfloat *)(of + uniform_i64((int64_t)(row(up ? 0 : 1) + srow) * ld * 4) + o));
+                }
+            } else {
+                __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(uint32_t, p), rsrc, voff, srow * ld4, 2 /* nt */);
+            }
+        };
+        auto pass3 = [&](auto spc) {
+            constexpr bool SP = decltype(spc)::value;
+            const bool s0 = SP && l < 32;  // this lane holds slot 0
+            // slot 0's butterfly 32: its own constants row; its bins 32 + 64 (r - 4) and their mirrors
+            // 288 + 64 (7 - r) as rows from 64 (r - 4) and 64 (7 - r)
+            const float2 *stB = s0 ? s_all + 32 * F_SLOTW : stA;
+            auto rowA = [&](int h) { return 2 * wave + h; };
+            auto rowB = [&](int h) { return 64 - 2 * wave - h; };
+            auto rowA_hi = [&](int h) { return SP && h == 0 ? 32 : 2 * wave + h + 256; };
+            auto rowB_hi = [&](int h) { return SP && h == 0 ? 288 : 64 - 2 * wave - h; };
+            const uint32_t offA_hi = offA + (s0 ? 32u : 256u) * ld4, offB_hi = offB + (s0 ? 224u * ld4 : 0u);
+            float2 a[8], y[8];
+            read8(i3a, a);
+            read8(i3b, y);
+            lds_barrier();  // every wave has read the tile's pass-2 output: the frame regions are free
+            auto row4 = [](const float2 *p, int c) { return *reinterpret_cast<const float4 *>(p + c); };
+            {
+                float2 w[8], wb[8];  // pass-3 twiddles r = 1..7 at 0..6
 #pragma unroll
-        for (int r = 0; r < 4; ++r) {
-            const float2 wk = wpost[r];
-            float2 mm[2];
+                for (int r = 0; r < 8; r += 2) {
+                    const float4 w4 = row4(stA, r);
+                    w[r + 1] = make_float2(w4.x, w4.y);
+                    if (r < 6) w[r + 2] = make_float2(w4.z, w4.w);
+                    const float4 b4 = SP ? row4(stB, r) : w4;
+                    wb[r + 1] = make_float2(b4.x, b4.y);
+                    if (r < 6) wb[r + 2] = make_float2(b4.z, b4.w);
+                }
 #pragma unroll
-            for (int q = 0; q < 2; ++q) mm[q] = make_float2(dpp_f<0xB1>(v[q][7 - r].x), dpp_f<0xB1>(v[q][7 - r].y));
-            lane01_fix(mm[0].x, mm[0].y, mm[1].x, mm[1].y, v[0][(8 - r) & 7].x, v[0][(8 - r) & 7].y,
-                       v[1][(8 - r) & 7].x, v[1][(8 - r) & 7].y, v[0][7 - r].x, v[0][7 - r].y, v[1][7 - r].x,
-                       v[1][7 - r].y);
+                for (int r = 1; r < 8; ++r) {
+                    a[r] = cmul(a[r], w[r]);
+                    y[r] = cmulc(y[r], wb[r]);
+                }
+            }
+            dft8(a, hs);
+            dft8(y, hs);
+            float2 wp[8];  // post twiddles at 8..11; SP: those of r >= 4 from B's row
 #pragma unroll
-            for (int q = 0; q < 2; ++q) {
-                const float2 m = mm[q];
-                const float2 z = v[q][r];
-                const float2 e = make_float2(z.x + m.x, z.y - m.y);
-                const float2 o = make_float2(z.y + m.y, m.x - z.x);  // -i (z - conj m)
-                const float2 t = cmul(wk, o);
-                float2 X1 = cadd(e, t);
-                const float2 X2 = csub(e, t);
-                if constexpr (IO::kInt) {
-                    if (r == 0) {  // bins 0, 1: X' -= (b / 1024) 2 ws W_k, the mean's fractional part
-                        X1.x = __builtin_fmaf(-rb[q], dcw.x, X1.x);
-                        X1.y = __builtin_fmaf(-rb[q], dcw.y, X1.y);
+            for (int r = 0; r < 4; r += 2) {
+                const float4 w4 = row4(stA, 8 + r);
+                wp[r] = make_float2(w4.x, w4.y);
+                wp[r + 1] = make_float2(w4.z, w4.w);
+                const float4 b4 = SP ? row4(stB, 8 + r) : w4;
+                wp[r + 4] = make_float2(b4.x, b4.y);
+                wp[r + 5] = make_float2(b4.z, b4.w);
+            }
+            float rbv = 0.f;
+            if constexpr (SP && IO::kInt) rbv = rbuf[tpar * F_TT + frm];
+            const float2 dcw = s0 ? dcw0 : dcw1;
+            const float sc0 = s0 ? 0.5f : 1.0f;
+#pragma unroll
+            for (int r = 0; r < 8; ++r) {
+                float2 z = a[r], m = y[(8 - r) & 7];
+                if constexpr (SP) {
+                    if (r < 4) {
+                        if (s0) m = a[(8 - r) & 7];
+                    } else if (s0) {
+                        z = y[r - 3];
+                        m = y[(12 - r) & 7];
                     }
                 }
-                pa[q][r] = X1.x * X1.x + X1.y * X1.y;
-                pb[q][r] = X2.x * X2.x + X2.y * X2.y;
-                if (r == 0) {
-                    pa[q][r] *= sc0;
-                    pb[q][r] *= sc0;
+                const float2 e = make_float2(z.x + m.x, z.y - m.y);
+                const float2 o = make_float2(z.y + m.y, m.x - z.x);  // -i (z - conj m)
+                float2 t = cmul(wp[r], o);
+                if (r >= 4) t = mul_mi(t);
+                float2 X1 = cadd(e, t);
+                const float2 X2 = csub(e, t);
+                if constexpr (SP && IO::kInt) {
+                    if (r == 0) {  // bins 0, 1: X' -= (b / 1024) 2 ws W_k, the mean's fractional part
+                        X1.x = __builtin_fmaf(-rbv, dcw.x, X1.x);
+                        X1.y = __builtin_fmaf(-rbv, dcw.y, X1.y);
+                    }
+                }
+                float p1 = X1.x * X1.x + X1.y * X1.y, p2 = X2.x * X2.x + X2.y * X2.y;
+                if (SP && r == 0) {
+                    p1 *= sc0;
+                    p2 *= sc0;
+                }
+                if (SP && r >= 4) {
+                    put(p1, offA_hi, rowA_hi, 64 * (r - 4), true);
+                    put(p2, offB_hi, rowB_hi, 64 * (7 - r), true);
+                } else {
+                    put(p1, offA, rowA, 64 * r);
+                    put(p2, offB, rowB, 64 * (7 - r));
                 }
             }
-        }
-#pragma unroll
-        for (int q = 0; q < 2; ++q) {  // lane 0: X'[256] = 2 conj(Z[256]) → |X'|^2 = 4 |Z[256]|^2
-            const float2 z = v[q][4];
-            p256[q] = (z.x * z.x + z.y * z.y) * 4.0f;
-        }
-        lds_barrier();  // the previous tile's write-out has finished reading the tile
-        // tile_at(pi + 64 r, wcol) and tile_at(512 - pi - 64 r, wcol): the rotations depend on the
-        // row mod 64 only, i.e. on pi
-        const int mb = (512 - pi) & 63;
-        const int ta = tile_at(pi, wcol), tb = tile_at(mb, wcol) + (512 - pi - mb) * F_PITCH;
-#pragma unroll
-        for (int r = 0; r < 4; ++r) {
-            *reinterpret_cast<float2 *>(&tile[ta + 64 * r * F_PITCH]) = make_float2(pa[0][r], pa[1][r]);
-            *reinterpret_cast<float2 *>(&tile[tb - 64 * r * F_PITCH]) = make_float2(pb[0][r], pb[1][r]);
-        }
-        if (l == 0) *reinterpret_cast<float2 *>(&tile[tile_at(256, wcol)]) = make_float2(p256[0], p256[1]);
-        lds_barrier();  // tile complete
-        prev = cur;
-        have_prev = 1;
-        asm("" : "+s"(have_prev));  // stays a scalar register
+            if constexpr (SP) {
+                if (s0) put((a[4].x * a[4].x + a[4].y * a[4].y) * 4.0f, offA, rowA, 256);  // bin 256
+            }
+        };
+        if (wave == 0) pass3(std::true_type{});
+        else pass3(std::false_type{});
+        tpar ^= 1;
         cur = nxt;
         if (!has_next) break;
         if constexpr (DYN) {
@@ -549,7 +571,6 @@ __global__ __launch_bounds__(F_NW * 64, 1) void stft1024_kernel(
         tl = ntl;
         te = nte;
     }
-    write_out(prev, std::integral_constant<int, 0>{}, std::integral_constant<int, 5>{});  // the last tile (complete since the loop's final barrier)
 }
 
 template <typename T>

@@ -8,6 +8,10 @@
 //   3: mode 0 with nontemporal stores
 //   4: mode 0 with tiles assigned round-robin so that the 8 XCD-neighbour WGs write
 //      adjacent tiles of the same rows (tile = wg + k*grid)
+//   5: one dword per lane, nontemporal: lanes 0-31 write one 128-B row segment (lane = column) and
+//      lanes 32-63 another row's; half-wave s of the 32 owns rows s + 64 r and 64 - s + 64 (7 - r)
+//      (s = 0: rows 64 r, 32 + 64 r and 512), 16 or 17 store instructions per wave and tile --
+//      stft1024_kernel's pass-3-by-bin pattern, stores straight from registers
 #include <hip/hip_runtime.h>
 #include <cstdio>
 #include <cstdint>
@@ -31,6 +35,18 @@ __global__ __launch_bounds__(1024) void wr(float *out, int64_t ld, int64_t tiles
         if (tl >= ntiles) break;
         const int64_t f = tl / tiles_per_file, ti = tl % tiles_per_file;
         float *of = out + f * (int64_t)K * ld + ti * tt;
+        if (mode == 5) {
+            const int s = tid >> 5, c = tid & 31;
+#pragma unroll
+            for (int i = 0; i < 17; ++i) {
+                int k;
+                if (i == 16) k = s == 0 ? 512 : -1;
+                else if (s == 0) k = i < 8 ? 64 * i : 32 + 64 * (i - 8);
+                else k = i < 8 ? s + 64 * i : 64 - s + 64 * (15 - i);
+                if (k >= 0) __builtin_nontemporal_store((float)k + (float)tl, of + (int64_t)k * ld + c);
+            }
+            continue;
+        }
         const int q = tid % segs;
         for (int k0 = 0; k0 < K; k0 += rows_per_pass) {
             const int k = k0 + tid / segs;
@@ -57,8 +73,9 @@ int main() {
     hipEvent_t e0, e1;
     hipEventCreate(&e0);
     hipEventCreate(&e1);
-    const char *names[] = {"128B segments", "256B segments", "contiguous float4", "128B nontemporal", "128B XCD-adjacent"};
-    for (int mode = 0; mode < 5; ++mode) {
+    const char *names[] = {"128B segments", "256B segments", "contiguous float4", "128B nontemporal", "128B XCD-adjacent",
+                           "128B dword/lane nt"};
+    for (int mode = 0; mode < 6; ++mode) {
         const int tt = mode == 1 ? 64 : 32;
         const int64_t tpf = ld / tt, ntiles = tpf * nfiles;
         const int grid = 256;
