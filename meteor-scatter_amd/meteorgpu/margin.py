@@ -15,15 +15,17 @@ The bound (standard floating-point error model, u = 2^-53):
 * a computed bin differs from the exact DFT by at most ``c * u * S`` with
   ``S = sum_j |x_j w_j| <= max|x| * sum(w)`` over the L samples used and ``c`` the longest chain
   of roundings an input term passes through: pocketfft's real FFT ``4 log2(Nf) + 8``; the
-  Goertzel segments ``3 L_seg G + 24`` (L_seg samples per lane, G = min(1/|sin theta|, L_seg)
-  the recurrence's error gain at bin angle theta, 24 for the rotations and the 16-lane sum), or,
-  for int16 blocks on the exact integer path (csrc/block_i8.hip), ``10.25 L / sum(w)`` (its
-  coefficients' 2^-55 quantisation is absolute, not relative to the window) -- the larger of
-  the two;
+  Goertzel segments ``3 L_seg G + 24`` (L_seg = 16 ... 256 samples per lane, all of which a lane
+  runs whatever L; G = min(1/|sin theta|, L_seg) the recurrence's error gain at bin angle theta,
+  24 for the rotations and the 16-lane sum; the generic rotation kernel that takes plans above
+  64 bins runs half as many samples per lane and stays below that), or, for int16 blocks on
+  the exact integer path (csrc/block_i8.hip), ``10.25 L / sum(w)`` (its coefficients' 2^-55
+  quantisation is absolute, not relative to the window) -- the larger of the two;
 * a band energy E = sum |X_k|^2 + 1e-12 over n bins then moves by at most
   ``dE = 2 sqrt(n E) dX + n dX^2 + (n + 2) u E``;
-* its dB value by at most ``10/ln 10 * r / (1 - r) + 2 u`` with r = dE / E (unbounded when
-  r >= 1: a band with no energy is never trusted);
+* its dB value by at most ``10/ln 10 * r / (1 - r) + 4 u (|dB| + 1)`` with r = dE / E (unbounded
+  when r >= 1: a band with no energy is never trusted; the second term is 10 log10's own rounding,
+  which is relative to the dB value: at -120 dB or at int32 full scale it is the larger one);
 * delta by the sum of the band's and the noise band's;
 * a threshold ``mean + k std`` over a window moves by at most (1 + k) max |d delta| (the mean
   and the population std are 1-Lipschitz in the max norm);
@@ -88,24 +90,35 @@ def _i8_chain(L: int, nbins: int, wsum: float) -> float:
     return 10.25 * float(L) / wsum if wsum > 0 else 0.0  # sum w = 0: every coefficient is 0, X = 0
 
 
+def _block_spl(L: int) -> int:
+    """samples per lane of the 16-lane Goertzel kernel (msd_block_plan_create): every lane runs all
+    of them, whatever L (a short or ragged block only zero-fills them)"""
+    return 16 if L <= 256 else 32 if L <= 512 else 64 if L <= 1024 else 128 if L <= 2048 else 256
+
+
 def _chain(nfft: int, L: int, bins: np.ndarray, wsum: float) -> float:
     """c: longest rounding chain of a bin (pocketfft + the device's transform: the Goertzel
-    segments or, for int16 blocks of the int8 path's shapes, its quantisation -- the larger, so
-    the bound holds whichever path ran)."""
-    l_seg = max(1, -(-int(L) // 16))  # samples per lane: the block_delta kernel's 16 lanes
-    dev = max(_goertzel_chain(l_seg, bins, nfft), _i8_chain(L, len(bins), wsum))
+    segments over the SPL samples a lane runs or, for int16 blocks of the int8 path's shapes, its
+    quantisation -- the larger, so the bound holds whichever path ran).  The generic rotation
+    kernel (csrc/block_delta.hip block_delta_kernel: above 64 bins or under MSD_OPT_GENERIC_STFT)
+    runs half as many samples per lane; its chain, counted in tests/band_signals.py, is
+    (3 sqrt 2 + 1) SPL / 2 + 11 - 2 sqrt 2 < 3 SPL + 24 at every L, so it needs no term here
+    (tests/test_band_signals.py holds that)."""
+    dev = max(_goertzel_chain(_block_spl(int(L)), bins, nfft), _i8_chain(L, len(bins), wsum))
     return 4.0 * math.log2(nfft) + 8.0 + dev
 
 
 def band_db_error(e_db: np.ndarray, nbins: int, dx: float) -> np.ndarray:
     """Per-block bound on |10 log10 E_gpu - 10 log10 E_numpy| given the band's dB values."""
-    e = np.power(10.0, np.asarray(e_db, dtype=np.float64) / 10.0)
+    e_db = np.asarray(e_db, dtype=np.float64)
+    e = np.power(10.0, e_db / 10.0)
     if nbins <= 0:  # empty band: E = 1e-12 exactly on both sides
         return np.zeros_like(e)
     de = 2.0 * np.sqrt(nbins * e) * dx + nbins * dx * dx + (nbins + 2) * U * e
     with np.errstate(divide="ignore", invalid="ignore"):
         r = de / e
-        out = np.where(r < 1.0, DB * r / (1.0 - r) + 2.0 * U * DB, np.inf)
+        # 10 log10 E: the logarithm and the product round relative to |dB| on either side
+        out = np.where(r < 1.0, DB * r / (1.0 - r) + 4.0 * U * (np.abs(e_db) + 1.0), np.inf)
     return out
 
 
