@@ -91,8 +91,8 @@ int msd_memset_dev(msd_ctx *ctx, void *dst, int value, size_t bytes);
  * 512 or 1024 and at most 8 band + noise bins take the latter by default; A/B, both within the
  * near-tie bound of meteorgpu/margin.py).
  * MSD_OPT_WELCH_GOERTZEL = 1 → msd_welch_bands[_dev] / msd_welch_psd compute int16 samples with the
- * float64 Goertzel kernel instead of the exact int8-MFMA one (plans with nperseg a multiple of 64
- * up to 512, <= 16 segments per block and a window in [-1, 1] take the latter by default; A/B,
+ * float64 Goertzel kernel instead of the exact int8-MFMA one (plans with nperseg 64, 128, 192, 256
+ * or 512, <= 16 segments per block and a window in [-1, 1] take the latter by default; A/B,
  * both within margin.py's live bound).
  *
  * Test hooks (per context; results must agree with the default):
@@ -469,6 +469,13 @@ int msd_welch_bands(msd_welch_plan *plan, const void *x, int dtype, int64_t n, d
 /* single signal, host buffers: the per-block PSD of the band bins, psd [nb][nslots] (one band
  * 0..nfft/2 and block_size = n gives scipy.signal.welch(x, fs, ...)'s whole PSD) */
 int msd_welch_psd(msd_welch_plan *plan, const void *x, int dtype, int64_t n, double *psd, int64_t *blocks);
+
+/* The integer coefficients the exact int8-MFMA band kernels are built from (host only: no context,
+ * no GPU), so that a test can restate their arithmetic in integers.  kind 0: the block plan's
+ * T_n = round(w_n cos(2 pi k n / nfft) 2^54) (part 0) or round(-w_n sin(...) 2^54) (part 1);
+ * kind 1: the Welch plan's T_n ~ (w_n e^{-2 pi i k n / nfft} - W_k / L) 2^53, real (part 0) or
+ * imaginary part, rounded so that sum_n T_n = 0.  window: L float64 in [-1, 1]; T: L values. */
+int msd_i8_coeffs(int kind, const double *window, int L, int nfft, int k, int part, int64_t *T);
 
 /* --------------------------------------------- a9: live detector state machine
  * Replaces processor.py:391-507 (states aggregates.py:4-24) over per-block band dB

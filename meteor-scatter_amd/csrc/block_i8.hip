@@ -206,16 +206,13 @@ int block_i8_build(msd_block_plan *p, const double *window, const int *bins, int
     const int ncomp = 2 * nbins;
     std::vector<int8_t> dig((size_t)BI_ND * 16 * L, 0);  // [digit][component][n]
     std::vector<int> init(BI_ND * 16, 0);
+    std::vector<int64_t> T(L);
     for (int cp = 0; cp < ncomp; ++cp) {
-        const int64_t k = bins[cp >> 1];
+        // round(w_n cos(2 pi k n / Nf) 2^54) (re), of -w_n sin (im)
+        block_i8_coeffs(window, L, nfft, bins[cp >> 1], cp & 1, T.data());
         for (int n = 0; n < L; ++n) {
-            // w_n cos(2 pi k n / Nf) (re), -w_n sin (im): the argument reduced exactly, long double
-            const int64_t m = (k * n) % nfft;
-            const long double a = 2.0L * 3.14159265358979323846264338327950288L * (long double)m / (long double)nfft;
-            const long double v = (long double)window[n] * ((cp & 1) ? -sinl(a) : cosl(a));
-            const int64_t T = llroundl(v * 0x1p54L);
             int8_t d[BI_ND];
-            if (!balanced_digits(T, d)) return fail(MSD_ERR_INVALID, "block_i8: coefficient beyond 7 digits");
+            if (!balanced_digits(T[n], d)) return fail(MSD_ERR_INVALID, "block_i8: coefficient beyond 7 digits");
             for (int b = 0; b < BI_ND; ++b) {
                 dig[((size_t)b * 16 + cp) * L + n] = d[b];
                 init[b * 16 + cp] += 128 * d[b];
@@ -278,3 +275,16 @@ int launch_block_i8(msd_block_plan *p, const int16_t *x, const int64_t *off, con
 }
 
 }  // namespace msd
+
+// the integers the two band kernels' plans are built from (host only, no context): what a test
+// needs to restate their arithmetic exactly
+extern "C" int msd_i8_coeffs(int kind, const double *window, int L, int nfft, int k, int part, int64_t *T) {
+    using namespace msd;
+    if (!window || !T) return fail(MSD_ERR_INVALID, "msd_i8_coeffs: null");
+    if ((kind != 0 && kind != 1) || (part != 0 && part != 1) || L < 1 || nfft < 1 || k < 0 || k > nfft / 2)
+        return fail(MSD_ERR_INVALID, "msd_i8_coeffs: need kind, part in {0, 1}, L, nfft >= 1, 0 <= k <= nfft / 2");
+    if (!block_i8_window(window, L)) return fail(MSD_ERR_INVALID, "msd_i8_coeffs: window outside [-1, 1]");
+    if (kind == 0) block_i8_coeffs(window, L, nfft, k, part, T);
+    else if (!welch_i8_coeffs(window, L, nfft, k, part, T)) return fail(MSD_ERR_INVALID, "welch_i8: coefficient rounding");
+    return MSD_OK;
+}

@@ -14,7 +14,8 @@
 //   host_check fuzz SEED ITERS     mutated / truncated WAV images parsed and decoded in memory,
 //                                  random programs and refinement plans
 //   host_check i8 SEED ITERS       i8_digits.h: balanced_digits<6> / <7> over ITERS random T and the
-//                                  edges, zero_sum_round on detrended Hann coefficients, frag_sample
+//                                  edges, zero_sum_round on detrended Hann coefficients, the two band
+//                                  kernels' coefficient functions, frag_sample
 #include <fcntl.h>
 #include <unistd.h>
 
@@ -438,6 +439,61 @@ bool check_zero_sum(int L, int k, bool im, std::string &why) {
     return true;
 }
 
+// block_i8_coeffs / welch_i8_coeffs (the plans' builders and msd_i8_coeffs call them) on the periodic
+// Hann window of length L zero-padded to nfft: every T in seven balanced digits; the block T within
+// 1/2 of w cos 2^54 and equal to round(w 2^54) at bin 0; the Welch T summing to zero, within 1 of the
+// detrended coefficient times 2^53, all zero for an all-zero window
+bool check_coeffs(int L, int nfft, int k, int part, std::string &why) {
+    const long double tau = 6.283185307179586476925286766559005768L;
+    std::vector<double> w(L);
+    for (int n = 0; n < L; ++n) w[n] = (double)(0.5L - 0.5L * cosl(tau * n / L));
+    const std::string at = "L " + std::to_string(L) + " nfft " + std::to_string(nfft) + " bin " + std::to_string(k) +
+                           (part ? " im" : " re");
+    std::vector<int64_t> Tb(L), Tw(L);
+    msd::block_i8_coeffs(w.data(), L, nfft, k, part, Tb.data());
+    if (!msd::welch_i8_coeffs(w.data(), L, nfft, k, part, Tw.data())) {
+        why = "welch_i8_coeffs refused " + at;
+        return false;
+    }
+    std::vector<long double> c(L);
+    long double W = 0.0L;
+    for (int n = 0; n < L; ++n) {
+        const long double a = tau * (long double)((int64_t)k * n % nfft) / nfft;
+        c[n] = (long double)w[n] * (part ? -sinl(a) : cosl(a));
+        W += c[n];
+    }
+    int64_t sum = 0;
+    for (int n = 0; n < L; ++n) {
+        int8_t d[7];
+        if (!msd::balanced_digits<7>(Tb[n], d) || !msd::balanced_digits<7>(Tw[n], d)) {
+            why = "a coefficient beyond 7 digits at " + at;
+            return false;
+        }
+        // 0.5 + the difference of the two angle reductions (a few 2^-64 of 2^54)
+        if (!(fabsl((long double)Tb[n] - c[n] * 0x1p54L) <= 0.5L + 0x1p-6L) ||
+            !(fabsl((long double)Tw[n] - (c[n] - W / L) * 0x1p53L) < 1.0L + 0x1p-6L)) {
+            why = "a coefficient off its value at " + at + " n " + std::to_string(n);
+            return false;
+        }
+        if (k == 0 && Tb[n] != (part ? 0 : (int64_t)llroundl((long double)w[n] * 0x1p54L))) {
+            why = "block bin 0 is not the window at " + at;
+            return false;
+        }
+        sum += Tw[n];
+    }
+    if (sum != 0) {
+        why = "welch_i8_coeffs: sum " + std::to_string(sum) + " at " + at;
+        return false;
+    }
+    std::vector<double> z(L, 0.0);
+    if (!msd::welch_i8_coeffs(z.data(), L, nfft, k, part, Tw.data()) ||
+        std::any_of(Tw.begin(), Tw.end(), [](int64_t t) { return t != 0; })) {
+        why = "welch_i8_coeffs: an all-zero window at " + at;
+        return false;
+    }
+    return true;
+}
+
 int cmd_i8(uint64_t seed, int64_t iters) {
     std::string why;
     auto both = [&](int64_t T) { return check_digits<6>(T, why) && check_digits<7>(T, why); };
@@ -472,6 +528,14 @@ int cmd_i8(uint64_t seed, int64_t iters) {
                     std::printf("bad %s\n", why.c_str());
                     return 1;
                 }
+    for (int L : {64, 192, 256})
+        for (int nfft : {L, 4096})
+            for (int k : {0, 1, nfft / 4, nfft / 2 - 1, nfft / 2})
+                for (int part = 0; part < 2; ++part)
+                    if (!check_coeffs(L, nfft, k, part, why)) {
+                        std::printf("bad %s\n", why.c_str());
+                        return 1;
+                    }
     // frag_sample: (g, j) onto the 64 samples of each K step, one to one
     for (int ks = 0; ks < 16; ++ks) {
         bool seen[64] = {};

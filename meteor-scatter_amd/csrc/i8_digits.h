@@ -3,7 +3,9 @@
 // coefficient T is ND balanced base-256 digits in [-128, 127], and a lane's 16-byte fragment of a
 // K step of 64 samples holds 8 samples at 8 g and 8 at 32 + 8 g (g = lane >> 4).  The device part
 // splits the samples; the host part (plain C++: host_check.cpp compiles it with g++ under the
-// sanitizers) expands the coefficients and maps fragment bytes to samples.
+// sanitizers) computes the band kernels' integer coefficients (the plans' builders and msd_i8_coeffs
+// share these functions, so a test restates the kernels from the very integers they run on), expands
+// them into digits and maps fragment bytes to samples.
 #pragma once
 
 #if defined(__HIPCC__)
@@ -76,6 +78,54 @@ inline bool zero_sum_round(const std::vector<long double> &v, std::vector<int64_
     if (R < 0 || R > L) return false;
     std::stable_sort(idx.begin(), idx.end(), [&](int a, int b) { return frac[a] > frac[b]; });
     for (int64_t r = 0; r < R; ++r) T[idx[r]] += 1;
+    return true;
+}
+
+// cos and sin of 2 pi j / N for any integer j, for host-built twiddle tables: j is reduced mod N into
+// [-N/2, N/2] in exact integer arithmetic, the angle and the functions are evaluated in long double
+// (x86-64: 64-bit significand), so each value rounded to double is within ~0.5 ulp of the exact one.
+// (A double angle 2 pi m / N up to 2 pi is itself off by up to ~2 pi u, several u of twiddle error.)
+inline void unit_root_ld(int64_t j, int64_t N, long double &c, long double &s) {
+    int64_t r = j % N;
+    if (r < 0) r += N;
+    if (2 * r > N) r -= N;
+    const long double a = 6.283185307179586476925286766559005768L * (long double)r / (long double)N;
+    c = cosl(a);
+    s = sinl(a);
+}
+
+// block_i8.hip's integers of bin k: T_n = round(w_n cos(2 pi k n / nfft) 2^54) (part 0, the real
+// part) or round(-w_n sin(...) 2^54) (part 1), n < L; the argument reduced exactly into [0, 2 pi),
+// long double
+inline void block_i8_coeffs(const double *window, int L, int nfft, int64_t k, int part, int64_t *T) {
+    for (int n = 0; n < L; ++n) {
+        const int64_t m = (k * n) % nfft;
+        const long double a = 2.0L * 3.14159265358979323846264338327950288L * (long double)m / (long double)nfft;
+        const long double v = (long double)window[n] * (part ? -sinl(a) : cosl(a));
+        T[n] = llroundl(v * 0x1p54L);
+    }
+}
+
+// welch_i8.hip's integers of bin k: c'_n = w_n e^{-i theta n} - W_k / L (W_k = sum_n w_n e^{-i theta n},
+// theta = 2 pi k / nfft, long double: the segment detrend folded in), its real (part 0) or
+// imaginary part rounded to T_n ~ c'_n 2^53 with sum_n T_n = 0 (zero_sum_round); false if that
+// rounding refuses
+inline bool welch_i8_coeffs(const double *window, int L, int nfft, int64_t k, int part, int64_t *T) {
+    long double Wre = 0.0L, Wim = 0.0L;
+    std::vector<long double> cr(L), ci(L), cv(L);
+    for (int n = 0; n < L; ++n) {
+        long double cs, sn;
+        unit_root_ld(k * n, nfft, cs, sn);
+        cr[n] = (long double)window[n] * cs;
+        ci[n] = -(long double)window[n] * sn;
+        Wre += cr[n];
+        Wim += ci[n];
+    }
+    const long double Wc = (part ? Wim : Wre) / (long double)L;
+    for (int n = 0; n < L; ++n) cv[n] = (part ? ci[n] : cr[n]) - Wc;
+    std::vector<int64_t> Tv(L);
+    if (!zero_sum_round(cv, Tv)) return false;
+    std::copy(Tv.begin(), Tv.end(), T);
     return true;
 }
 

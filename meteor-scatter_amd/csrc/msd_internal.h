@@ -85,21 +85,6 @@ struct msd_ctx {
     int stream_eps_log2 = 0;       // MSD_OPT_STREAM_EPS_LOG2 (test hook): the stream's near-tie bound times 2^n
 };
 
-namespace msd {
-// cos and sin of 2 pi j / N for any integer j, for host-built twiddle tables: j is reduced mod N into
-// [-N/2, N/2] in exact integer arithmetic, the angle and the functions are evaluated in long double
-// (x86-64: 64-bit significand), so each value rounded to double is within ~0.5 ulp of the exact one.
-// (A double angle 2 pi m / N up to 2 pi is itself off by up to ~2 pi u, several u of twiddle error.)
-inline void unit_root_ld(int64_t j, int64_t N, long double &c, long double &s) {
-    int64_t r = j % N;
-    if (r < 0) r += N;
-    if (2 * r > N) r -= N;
-    const long double a = 6.283185307179586476925286766559005768L * (long double)r / (long double)N;
-    c = cosl(a);
-    s = sinl(a);
-}
-}  // namespace msd
-
 struct msd_stft_plan {
     msd_ctx *ctx = nullptr;
     int nperseg = 0, nfft = 0, hop = 0, M = 0;  // M = nfft/2 complex points, K = M + 1 bins

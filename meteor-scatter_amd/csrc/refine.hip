@@ -27,6 +27,7 @@
 #include <type_traits>
 #include <vector>
 
+#include "i8_digits.h"
 #include "msd_internal.h"
 #include "refine_i8.h"
 #include "refine_plan.h"

@@ -16,8 +16,12 @@
 // round(sum_n (x_n - 128) T_n) = round(sum_n x_n T_n), zero for a silent block.  Error
 // against the exact DFT: the quantisation (|T - c' 2^53| < 1: 2^-53 sum|x|) and two roundings of
 // |X| <= 2 sum|x|, 5 u sum|x| -- inside margin.live_over_error's int8 term (18 u nperseg max|x|).
+// The path covers nperseg 64, 128, 192, 256 and 512 (1, 2, 3, 4 and 8 K steps: the instantiations
+// below) with 1 to 16 segments per block; every other shape, nperseg 320, 384 and 448 included,
+// keeps the float64 Goertzel kernel (welch_i8_shape).  tests/test_gpu_i8_exact.py holds the psd
+// bit for bit to this arithmetic restated in integers (tests/i8_exact.py).
 //
-// GEMM: rows = segments (a 16-row tile holds bpt = 16 / nseg whole blocks, nseg rows each; the
+// GEMM: rows = segments (a 16-row tile holds bpt = min(8, 16 / nseg) whole blocks, nseg rows each; the
 // 5-segment instantiation walks units of 16 blocks = 5 full tiles, see NSEG == 5 below),
 // K = nperseg samples in steps of 64 (the lane's A fragment: 16 samples of its row, 8 at 8 g and 8 at
 // 32 + 8 g of the step, g = lane >> 4, as block_i8.hip), columns = the components of the band bins
@@ -73,7 +77,7 @@ constexpr int WI_MAXKS = 8;               // nperseg <= 512 (16 K steps would sp
 
 struct WelchI8Args {
     int64_t nfiles, max_blocks, ld;
-    int block_size, step, nseg, bpt;  // bpt: whole blocks per 16-row tile (bpt * nseg <= 16 rows)
+    int block_size, step, nseg, bpt;  // bpt: whole blocks per 16-row tile (bpt * nseg <= 16 rows, bpt <= 8)
     int nct, cg, ngroups, reps;       // column tiles, tiles per group, groups, workgroups per group and XCD
     int nslots;
     double xscale;  // 2^-53 x sample_scale: a component's value from its integer digit sum
@@ -485,10 +489,13 @@ __global__ __launch_bounds__(256) void welch_i8_bands_kernel(const int64_t *__re
 
 }  // namespace
 
-// the int8 path applies: int16 samples (checked at launch), nperseg a multiple of 64 up to 512, at
+// the int8 path applies: int16 samples (checked at launch), nperseg 64, 128, 192, 256 or 512 (the
+// K step counts launch_welch_i8 instantiates; 320, 384 and 448 keep the float64 Goertzel kernel), at
 // most 16 segments per block, a window in [-1, 1] (the quantisation and margin.py's bound), >= 1 bin
 bool welch_i8_shape(const msd_welch_cfg &c, int nseg, int nslots, const double *window) {
-    if (c.nperseg % 64 != 0 || c.nperseg > 64 * WI_MAXKS || nseg < 1 || nseg > 16 || nslots < 1) return false;
+    const int KS = c.nperseg / 64;
+    if (c.nperseg % 64 != 0 || !(KS >= 1 && (KS <= 4 || KS == WI_MAXKS)) || nseg < 1 || nseg > 16 || nslots < 1)
+        return false;
     for (int n = 0; n < c.nperseg; ++n)
         if (!std::isfinite(window[n]) || std::fabs(window[n]) > 1.0) return false;
     return true;
@@ -515,26 +522,12 @@ int welch_i8_build(msd_welch_plan *p, const double *window) {
     std::vector<double> dbl((size_t)nct * 8, 0.0);
     for (int s = 0; s < nslots; ++s) dbl[s] = dblv[s];
     std::vector<int8_t> dig((size_t)WI_ND * L);
-    std::vector<long double> cv(L);
     std::vector<int64_t> T(L);
     bool pairs = true;
     for (int cp = 0; cp < ncomp; ++cp) {
-        const int64_t k = ks_bins[cp >> 1];
-        const bool im = cp & 1;
-        // W_k = sum_n w_n e^{-i theta n} in long double; c'_n = w_n e^{-i theta n} - W_k / L
-        long double Wre = 0.0L, Wim = 0.0L;
-        std::vector<long double> cr(L), ci(L);
-        for (int n = 0; n < L; ++n) {
-            long double cs, sn;
-            unit_root_ld(k * n, nfft, cs, sn);
-            cr[n] = (long double)window[n] * cs;
-            ci[n] = -(long double)window[n] * sn;
-            Wre += cr[n];
-            Wim += ci[n];
-        }
-        const long double Wc = (im ? Wim : Wre) / (long double)L;
-        for (int n = 0; n < L; ++n) cv[n] = (im ? ci[n] : cr[n]) - Wc;
-        if (!zero_sum_round(cv, T)) return fail(MSD_ERR_INVALID, "welch_i8: coefficient rounding");
+        // c'_n = w_n e^{-i theta n} - W_k / L, rounded to sum to zero
+        if (!welch_i8_coeffs(window, L, nfft, ks_bins[cp >> 1], cp & 1, T.data()))
+            return fail(MSD_ERR_INVALID, "welch_i8: coefficient rounding");
         for (int n = 0; n < L; ++n) {
             int8_t d[WI_ND];
             if (!balanced_digits(T[n], d)) return fail(MSD_ERR_INVALID, "welch_i8: coefficient beyond 7 digits");
@@ -592,7 +585,7 @@ int launch_welch_i8(msd_welch_plan *p, const int16_t *x, const int64_t *off, con
     A.block_size = c.block_size;
     A.step = p->step;
     A.nseg = p->nseg;
-    A.bpt = 16 / p->nseg;
+    A.bpt = std::min(8, 16 / p->nseg);  // the averaging lanes l >> 3 cover 8 blocks: one segment per block fills 8 rows
     A.nct = nct;
     const int nw = wi_waves(KS);
     // per column tile: its B fragments, its 8 power scales, and every wave's 8 carried block sums

@@ -221,6 +221,7 @@ _SIGS = [
     ("msd_welch_bands_dev", C.c_int, [_P, _P, C.c_int, _P, _P, C.c_int64, C.c_int64, _P, C.c_int64, _P]),
     ("msd_welch_bands", C.c_int, [_P, _P, C.c_int, C.c_int64, _P, C.POINTER(C.c_int64)]),
     ("msd_welch_psd", C.c_int, [_P, _P, C.c_int, C.c_int64, _P, C.POINTER(C.c_int64)]),
+    ("msd_i8_coeffs", C.c_int, [C.c_int, _P, C.c_int, C.c_int, C.c_int, C.c_int, _P]),
     ("msd_live_detect_dev", C.c_int,
      [_P, _P, _P, C.c_int64, C.c_int64, C.POINTER(MsdLiveCfg), _P, C.c_int64, _P, _P, _P, _P]),
     ("msd_live_detect", C.c_int,
@@ -628,6 +629,18 @@ class WelchPlan:
                 max_blocks: int, band_db: DeviceBuffer, ld: int, psd: DeviceBuffer | None = None):
         check(self.ctx.lib.msd_welch_bands_dev(self.h, x.ptr, dtype_code(dtype), off.ptr, length.ptr, int(nfiles),
                                                int(max_blocks), band_db.ptr, int(ld), psd.ptr if psd else None))
+
+
+I8_BLOCK, I8_WELCH = 0, 1
+
+
+def i8_coeffs(kind: int, window: np.ndarray, nfft: int, k: int, part: int) -> np.ndarray:
+    """msd_i8_coeffs: the int64 coefficients T_n of bin k's real (part 0) or imaginary (part 1)
+    component in the block (I8_BLOCK) or Welch (I8_WELCH) int8-MFMA plan (host only)"""
+    w = np.ascontiguousarray(window, dtype=np.float64)
+    T = np.empty(w.shape[0], np.int64)
+    check(load().msd_i8_coeffs(int(kind), ptr(w), int(w.shape[0]), int(nfft), int(k), int(part), ptr(T)))
+    return T
 
 
 def live_detect(ctx: Context, band_db: np.ndarray, cfg: MsdLiveCfg, cap: int | None = None):

@@ -59,3 +59,5 @@ def test_invalid_args_fail_without_gpu():
     assert b"null" in lib.msd_last_error()
     assert lib.msd_stream_wait(None, None) == _lib.MSD_ERR_INVALID
     assert b"msd_stream_wait" in lib.msd_last_error()
+    assert lib.msd_i8_coeffs(0, None, 64, 64, 0, 0, None) == _lib.MSD_ERR_INVALID  # host only: no context
+    assert b"msd_i8_coeffs" in lib.msd_last_error()

@@ -183,6 +183,8 @@ def test_refine_plan_under_sanitizers(harness):
 def test_i8_digits_under_sanitizers(harness, seed):
     # i8_digits.h, the host half of the three int8-MFMA kernels' exactness argument: balanced_digits<6>
     # and <7> reproduce T or refuse it exactly when it does not fit, zero_sum_round's integers sum to 0
-    # within 1 of the scaled coefficients, frag_sample maps a K step's fragment bytes onto its samples
+    # within 1 of the scaled coefficients, block_i8_coeffs / welch_i8_coeffs (what the plans and
+    # msd_i8_coeffs compute) fit seven digits and sum to zero, frag_sample maps a K step's fragment
+    # bytes onto its samples
     out = run(harness, "i8", seed, 200000)
     assert out.startswith("ok") and out.split()[3] == "200000", out
