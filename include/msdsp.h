@@ -175,7 +175,12 @@ int msd_stft_psd_f64(msd_stft_plan *plan, const void *x, int dtype, int64_t n, d
  * block_size B = int(fs*block_duration_sec); nfft Nf (already doubled, main.py:353);
  * window: the first min(B, Nf) values of np.hanning(B) (float64);
  * band/noise: inclusive bin ranges [lo, hi] of rfftfreq(Nf, 1/fs) selected by the
- * reference masks (hi < lo means an empty band → energy 1e-12). Arithmetic is float64. */
+ * reference masks (hi < lo means an empty band → energy 1e-12). Arithmetic is float64.
+ * L = min(B, Nf) <= 65536 (above: MSD_ERR_UNSUPPORTED), at most 4096 bins in the two bands
+ * together.  Three float64 kernels serve a plan (block_delta.hip): up to L = 4096 a 16-lane
+ * Goertzel per block for up to 64 bins and a rotation recurrence, one wave per block, above
+ * that; for 4096 < L <= 65536 a 256-lane Goertzel, one workgroup per block, for any bin count.
+ * int16 blocks of L = 256, 512 or 1024 with 1-8 bins run on the matrix cores (block_i8.hip). */
 int msd_block_plan_create(msd_ctx *ctx, int64_t block_size, int32_t nfft, const double *window, int32_t band_lo,
                           int32_t band_hi, int32_t noise_lo, int32_t noise_hi, msd_block_plan **out);
 void msd_block_plan_destroy(msd_block_plan *plan);

@@ -546,7 +546,7 @@ int msd_block_plan_create(msd_ctx *ctx, int64_t block_size, int32_t nfft, const 
     *out = nullptr;
     if (block_size <= 0 || nfft <= 0) return fail(MSD_ERR_INVALID, "block plan: block_size and n_fft must be > 0");
     const int64_t L = block_size < nfft ? block_size : nfft;
-    if (L > 4096) return fail(MSD_ERR_UNSUPPORTED, "block plan: min(block_size, n_fft) must be <= 4096");
+    if (L > BLOCK_MAX_L) return fail(MSD_ERR_UNSUPPORTED, "block plan: min(block_size, n_fft) must be <= 65536");
     if (!window) return fail(MSD_ERR_INVALID, "block plan: null window");
     const int K = nfft / 2 + 1;
     auto clampband = [&](int32_t &lo, int32_t &hi) {
@@ -579,7 +579,9 @@ int msd_block_plan_create(msd_ctx *ctx, int64_t block_size, int32_t nfft, const 
         tw[m] = make_double2(std::cos(a), std::sin(a));
     }
     // fast-path constants (block_delta.hip, block_delta2_kernel)
-    const int spl = L <= 256 ? 16 : L <= 512 ? 32 : L <= 1024 ? 64 : L <= 2048 ? 128 : 256;
+    const bool long_block = L > BLOCK_FAST_MAX_L;  // block_long_kernel: no rotation table (d_tw serves)
+    const int spl = long_block ? block_long_spl((int)L)
+                               : L <= 256 ? 16 : L <= 512 ? 32 : L <= 1024 ? 64 : L <= 2048 ? 128 : 256;
     p->spl = spl;
     std::vector<double> bconst;
     for (int k : bins) {
@@ -589,7 +591,7 @@ int msd_block_plan_create(msd_ctx *ctx, int64_t block_size, int32_t nfft, const 
         bconst.push_back(-std::sin(th));
     }
     for (int k : bins) {
-        for (int seg = 0; seg < 16; ++seg) {
+        for (int seg = 0; seg < 16 && !long_block; ++seg) {
             const int64_t m = ((int64_t)k * (seg * spl + spl - 1)) % nfft;
             const double a = -2.0 * M_PI * (double)m / (double)nfft;
             bconst.push_back(std::cos(a));

@@ -292,10 +292,190 @@ __global__ __launch_bounds__(256) void block_db_kernel(const double2 *__restrict
     delta[o] = bd - nd;
 }
 
-template <typename T, int SPL>
-int launch_bd2(msd_block_plan *p, const void *x, const int64_t *off, const int64_t *len, int64_t nfiles,
-               int64_t max_blocks, double *band_db, double *noise_db, double *delta, int64_t ld) {
-    const int64_t blocks = nfiles * max_blocks;
+// ---------------------------------------------------------------- long blocks
+// BLOCK_FAST_MAX_L < L <= BLOCK_MAX_L: the 16-lane Goertzel above widened to one 256-thread
+// workgroup per block, for any number of bins.  Lane l owns the SPL = block_long_spl(L) samples from
+// n0 = l SPL on (a runtime trip count; lanes past L skip the loop and add an exact 0), read in chunks
+// of 8: one 16-B load of int16 samples and four of the window, which no longer fits LDS and comes
+// from global memory (L2 / L1 hits after the block's first sweep).  A chunk that straddles L, or any
+// chunk of a block that does not start on a 16-B boundary (odd B), is read sample by sample with
+// index L and beyond as 0.  Bins are carried 8 per sweep; after its segment each lane rotates its
+// partial sum to the block origin by the plan's exactly reduced twiddle d_tw[k (n0 + SPL - 1) mod
+// nfft], the 64 lanes are summed by DPP (rows, then row broadcasts), the 4 waves through LDS, and |X|^2
+// goes to LDS.  Lane 0 of wave 0 sums the band, lane 0 of wave 1 the noise band (numpy's pairwise
+// order); block_db_kernel makes the dB values.
+//
+// Rounding chain from a sample to a bin (tests/band_signals.py's rules): the recurrence over the SPL
+// steps a lane runs, 3 SPL G, and the 24 of the 16-lane kernel for the window product, the
+// rotation, its 4-add lane sum and |X|^2, plus the 4 further adds of 256 lanes (6 in the wave, 2
+// across the waves): 3 SPL G + 28 (margin._chain, tests/long_block_signals.py).
+constexpr int BDL_SW = 8;  // bins per sweep
+
+// (k n) mod nfft for 0 <= k n < 2^53: the quotient from a float64 product is off by at most one
+__device__ __forceinline__ int bdl_mulmod(int k, int n, int nfft, double inv_nfft) {
+    const int64_t prod = (int64_t)k * n;
+    int64_t r = prod - (int64_t)((double)prod * inv_nfft) * nfft;
+    if (r < 0) r += nfft;
+    if (r >= nfft) r -= nfft;
+    return (int)r;
+}
+
+// x of lane 15 (CTRL 0x142, row_bcast15) or lane 31 (0x143, row_bcast31) of the rows before, in the
+// rows of mask ROWS; 0 in the other rows
+template <int CTRL, int ROWS>
+__device__ __forceinline__ double dpp_bcast_d(double x) {
+    const int2 v = __builtin_bit_cast(int2, x);
+    int2 r;
+    r.x = __builtin_amdgcn_update_dpp(0, v.x, CTRL, ROWS, 0xf, false);
+    r.y = __builtin_amdgcn_update_dpp(0, v.y, CTRL, ROWS, 0xf, false);
+    return __builtin_bit_cast(double, r);
+}
+// the wave's sum, in lane 63 alone: the four row sums, row 0 into row 1 and row 2 into row 3, then
+// rows 0-1 into rows 2-3 (6 adds deep, no LDS round trip)
+__device__ __forceinline__ double wave_sum_dpp(double v) {
+    v = row_sum_d(v);
+    v += dpp_bcast_d<0x142, 0xa>(v);
+    v += dpp_bcast_d<0x143, 0xc>(v);
+    return v;
+}
+
+// 8 samples from an address aligned to min(16, 8 sizeof(T)) bytes
+template <typename T>
+__device__ __forceinline__ void bdl_load8(const T *__restrict__ p, double (&v)[8]) {
+    if constexpr (sizeof(T) == 1) {
+        union {
+            uint2 u;
+            T e[8];
+        } raw;
+        raw.u = *reinterpret_cast<const uint2 *>(p);
+#pragma unroll
+        for (int q = 0; q < 8; ++q) v[q] = to_d(raw.e[q]);
+    } else {
+        constexpr int NV = (int)sizeof(T) / 2;
+        union {
+            uint4 u[NV];
+            T e[8];
+        } raw;
+#pragma unroll
+        for (int i = 0; i < NV; ++i) raw.u[i] = reinterpret_cast<const uint4 *>(p)[i];
+#pragma unroll
+        for (int q = 0; q < 8; ++q) v[q] = to_d(raw.e[q]);
+    }
+}
+
+// One sweep: SW bins (j0 .. j0+SW-1, all < nbins) over the lane's segment, the rotation, the wave
+// sum, and the four waves' partial sums into `red` [4][BDL_SW].
+template <typename T, int SW>
+__device__ __forceinline__ void bdl_sweep(const T *__restrict__ xb, const double *__restrict__ g_win,
+                                          const double *__restrict__ bconst, const double2 *__restrict__ g_tw,
+                                          const int *__restrict__ bins, double2 *__restrict__ red, int j0, int n0,
+                                          int spl, int L, int nfft, double inv_nfft, bool aligned) {
+    double c2[SW], s1[SW], s2[SW];
+#pragma unroll
+    for (int t = 0; t < SW; ++t) {
+        c2[t] = bconst[3 * (j0 + t)];
+        s1[t] = 0.0;
+        s2[t] = 0.0;
+    }
+    if (n0 < L) {
+        for (int m0 = 0; m0 < spl; m0 += 8) {
+            const int n = n0 + m0;
+            double v[8];
+            if (aligned && n + 8 <= L) {
+                bdl_load8(xb + n, v);
+                double2 w[4];
+#pragma unroll
+                for (int i = 0; i < 4; ++i) w[i] = reinterpret_cast<const double2 *>(g_win + n)[i];
+#pragma unroll
+                for (int i = 0; i < 4; ++i) {  // block * np.hanning(B)
+                    v[2 * i] = v[2 * i] * w[i].x;
+                    v[2 * i + 1] = v[2 * i + 1] * w[i].y;
+                }
+            } else {
+#pragma unroll
+                for (int q = 0; q < 8; ++q) v[q] = n + q < L ? to_d(xb[n + q]) * g_win[n + q] : 0.0;
+            }
+#pragma unroll
+            for (int q = 0; q < 8; ++q) {
+#pragma unroll
+                for (int t = 0; t < SW; ++t) {
+                    const double s0 = BD2_STEP(c2[t], s1[t], s2[t], v[q]);
+                    s2[t] = s1[t];
+                    s1[t] = s0;
+                }
+            }
+        }
+    }
+    // y = s1 - e^{-i th} s2 = sum_m v_m e^{i th (spl-1-m)}; rotate by e^{-i th (n0+spl-1)}
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+#pragma unroll
+    for (int t = 0; t < SW; ++t) {
+        const double cth = bconst[3 * (j0 + t) + 1], msth = bconst[3 * (j0 + t) + 2];
+        const double yr = fma(-cth, s2[t], s1[t]);
+        const double yi = -msth * s2[t];
+        const double2 rot = g_tw[bdl_mulmod(bins[j0 + t], n0 + spl - 1, nfft, inv_nfft)];
+        const double re = wave_sum_dpp(fma(yr, rot.x, -yi * rot.y));
+        const double im = wave_sum_dpp(fma(yr, rot.y, yi * rot.x));
+        if (lane == 63) red[wave * BDL_SW + t] = make_double2(re, im);
+    }
+}
+
+template <typename T>
+__global__ __launch_bounds__(256) void block_long_kernel(
+    const T *__restrict__ x, const int64_t *__restrict__ off, const int64_t *__restrict__ len, int64_t nfiles,
+    int64_t blocks_per_file, int64_t B, int L, int nfft, int spl, const double *__restrict__ g_win,
+    const double *__restrict__ bconst, const double2 *__restrict__ g_tw, const int *__restrict__ bins, int nband,
+    int nnoise, double *__restrict__ energy) {
+    extern __shared__ double smem_d[];
+    double2 *red_all = reinterpret_cast<double2 *>(smem_d);  // [2][4][BDL_SW]: sweeps alternate halves
+    double *pb = smem_d + 2 * 2 * 4 * BDL_SW;                // [nbins] powers
+    const int tid = threadIdx.x;
+    const int n0 = tid * spl;
+    const int nbins = nband + nnoise;
+    const double inv_nfft = 1.0 / (double)nfft;
+    const int64_t nblocks = nfiles * blocks_per_file;
+    constexpr uintptr_t ALIGN = 8 * sizeof(T) < 16 ? 8 * sizeof(T) : 16;
+
+    for (int64_t gb = blockIdx.x; gb < nblocks; gb += gridDim.x) {
+        const int64_t f = gb / blocks_per_file;
+        const int64_t b = gb - f * blocks_per_file;
+        if (b >= len[f] / B) continue;  // uniform over the workgroup
+        const T *xb = x + off[f] + b * B;
+        const bool aligned = (reinterpret_cast<uintptr_t>(xb) & (ALIGN - 1)) == 0;
+
+        int par = 0;
+        for (int j0 = 0; j0 < nbins; j0 += BDL_SW, par ^= 1) {
+            double2 *red = red_all + par * 4 * BDL_SW;
+            const int sw = nbins - j0 < BDL_SW ? nbins - j0 : BDL_SW;  // uniform: no divergence
+            switch (sw) {
+                case 1: bdl_sweep<T, 1>(xb, g_win, bconst, g_tw, bins, red, j0, n0, spl, L, nfft, inv_nfft, aligned); break;
+                case 2: bdl_sweep<T, 2>(xb, g_win, bconst, g_tw, bins, red, j0, n0, spl, L, nfft, inv_nfft, aligned); break;
+                case 3: bdl_sweep<T, 3>(xb, g_win, bconst, g_tw, bins, red, j0, n0, spl, L, nfft, inv_nfft, aligned); break;
+                case 4: bdl_sweep<T, 4>(xb, g_win, bconst, g_tw, bins, red, j0, n0, spl, L, nfft, inv_nfft, aligned); break;
+                case 5: bdl_sweep<T, 5>(xb, g_win, bconst, g_tw, bins, red, j0, n0, spl, L, nfft, inv_nfft, aligned); break;
+                case 6: bdl_sweep<T, 6>(xb, g_win, bconst, g_tw, bins, red, j0, n0, spl, L, nfft, inv_nfft, aligned); break;
+                case 7: bdl_sweep<T, 7>(xb, g_win, bconst, g_tw, bins, red, j0, n0, spl, L, nfft, inv_nfft, aligned); break;
+                default: bdl_sweep<T, 8>(xb, g_win, bconst, g_tw, bins, red, j0, n0, spl, L, nfft, inv_nfft, aligned); break;
+            }
+            // one barrier per sweep: this half of `red` is next written two sweeps on, after the
+            // barrier of the sweep between, which the readers below reach only after their reads
+            __syncthreads();
+            if (tid < sw) {
+                const double2 a = red[tid], c = red[BDL_SW + tid], d = red[2 * BDL_SW + tid], e = red[3 * BDL_SW + tid];
+                const double re = (a.x + c.x) + (d.x + e.x);
+                const double im = (a.y + c.y) + (d.y + e.y);
+                pb[j0 + tid] = re * re + im * im;  // as block_delta2_kernel forms it
+            }
+        }
+        __syncthreads();
+        // np.sum(power[band]) + 1e-12 on one lane each (n <= 4096: one ufunc buffer, depth <= 6)
+        if (tid == 0) energy[2 * gb] = 0.0 + np_pairwise_iter<6>(ArrRef{pb}, 0, nband) + 1e-12;
+        if (tid == 64) energy[2 * gb + 1] = 0.0 + np_pairwise_iter<6>(ArrRef{pb}, nband, nnoise) + 1e-12;
+        __syncthreads();  // pb is rewritten for the next block
+    }
+}
+
+int ensure_energy(msd_block_plan *p, int64_t blocks) {
     if ((size_t)blocks + 1 > p->energy_cap) {  // grown once per plan (the stream is drained first);
         MSD_HIP(hipStreamSynchronize(p->ctx->stream));  // + 1: block_i8_kernel's spare slot
         MSD_HIP(hipFree(p->d_energy));
@@ -304,6 +484,36 @@ int launch_bd2(msd_block_plan *p, const void *x, const int64_t *off, const int64
         MSD_HIP(hipMalloc(&p->d_energy, sizeof(double2) * ((size_t)blocks + 1)));
         p->energy_cap = (size_t)blocks + 1;
     }
+    return MSD_OK;
+}
+
+// workgroups of block_long_kernel: a few per CU, each walking whole blocks
+inline int64_t bdl_grid(int64_t blocks, int num_cu) { return std::min<int64_t>(blocks, (int64_t)num_cu * 8); }
+
+template <typename T>
+int launch_bdl(msd_block_plan *p, const void *x, const int64_t *off, const int64_t *len, int64_t nfiles,
+               int64_t max_blocks, double *band_db, double *noise_db, double *delta, int64_t ld) {
+    const int64_t blocks = nfiles * max_blocks;
+    if (int rc = ensure_energy(p, blocks)) return rc;
+    const int nband = p->band_hi - p->band_lo + 1 > 0 ? p->band_hi - p->band_lo + 1 : 0;
+    const int nnoise = p->noise_hi - p->noise_lo + 1 > 0 ? p->noise_hi - p->noise_lo + 1 : 0;
+    const size_t lds = sizeof(double) * (2 * 2 * 4 * BDL_SW + (size_t)(p->nbins > 0 ? p->nbins : 1));
+    hipLaunchKernelGGL((block_long_kernel<T>), dim3((unsigned)bdl_grid(blocks, p->ctx->num_cu)), dim3(256), lds,
+                       p->ctx->stream, static_cast<const T *>(x), off, len, nfiles, max_blocks, p->block_size, p->L,
+                       p->nfft, p->spl, p->d_window, p->d_bconst, p->d_tw, p->d_bins, nband, nnoise,
+                       reinterpret_cast<double *>(p->d_energy));
+    MSD_HIP(hipGetLastError());
+    hipLaunchKernelGGL(block_db_kernel, dim3((unsigned)((blocks + 255) / 256)), dim3(256), 0, p->ctx->stream,
+                       p->d_energy, len, nfiles, max_blocks, p->block_size, band_db, noise_db, delta, ld);
+    MSD_HIP(hipGetLastError());
+    return MSD_OK;
+}
+
+template <typename T, int SPL>
+int launch_bd2(msd_block_plan *p, const void *x, const int64_t *off, const int64_t *len, int64_t nfiles,
+               int64_t max_blocks, double *band_db, double *noise_db, double *delta, int64_t ld) {
+    const int64_t blocks = nfiles * max_blocks;
+    if (int rc = ensure_energy(p, blocks)) return rc;
     // persistent grid: a few workgroups per CU, each walking groups of 16 blocks (4 resident per CU;
     // C3 A/B over two boxes, profiles/r4_bd2_grid_ab.txt: 4 per CU 0.409 ms, 8 0.381-0.393, 16 0.372-0.383,
     // 32 0.382, one per group 0.398)
@@ -381,6 +591,16 @@ int launch_block_delta(msd_block_plan *p, const void *x, int dtype, const int64_
     if (nband + nnoise > BD_MAXBINS)
         return fail(MSD_ERR_UNSUPPORTED, "block_delta: at most 4096 FFT bins in the two bands together");
     KernelTimer timer(p->ctx, K_BLOCK);
+    if (p->L > BLOCK_FAST_MAX_L) {  // one kernel for every bin count
+        switch (dtype) {
+            case MSD_U8: return launch_bdl<uint8_t>(p, x, off, len, nfiles, max_blocks, band_db, noise_db, delta, ld);
+            case MSD_I16: return launch_bdl<int16_t>(p, x, off, len, nfiles, max_blocks, band_db, noise_db, delta, ld);
+            case MSD_I32: return launch_bdl<int32_t>(p, x, off, len, nfiles, max_blocks, band_db, noise_db, delta, ld);
+            case MSD_F32: return launch_bdl<float>(p, x, off, len, nfiles, max_blocks, band_db, noise_db, delta, ld);
+            case MSD_F64: return launch_bdl<double>(p, x, off, len, nfiles, max_blocks, band_db, noise_db, delta, ld);
+            default: return fail(MSD_ERR_INVALID, "block_delta: unknown dtype");
+        }
+    }
     if (nband + nnoise <= BD2_MAXBINS && !p->ctx->force_generic) {
         switch (dtype) {
             case MSD_U8: return launch_bd2_t<uint8_t>(p, x, off, len, nfiles, max_blocks, band_db, noise_db, delta, ld);

@@ -121,8 +121,10 @@ struct msd_block_plan {
     int *d_bins = nullptr;                // [nbins] bin indices, band first
     // fast path (nbins <= 64): per bin {2cos th, cos th, -sin th}, then per (bin, 16-lane
     // segment) the rotation exp(-i th (seg*SPL + SPL - 1)) — host-computed in float64
+    // long blocks (L > 4096, block_long_kernel): the per-bin constants alone; a lane's rotation comes
+    // from d_tw
     double *d_bconst = nullptr;
-    int spl = 0;                          // samples per lane segment of the fast path
+    int spl = 0;                          // samples per lane segment of the fast path / the long kernel
     double2 *d_energy = nullptr;          // fast path: per block (band, noise) energy + 1e-12, grown
     size_t energy_cap = 0;                // blocks d_energy holds
     void *d_i8 = nullptr;                 // int16 blocks on the matrix cores (block_i8.hip): B fragments
@@ -279,6 +281,13 @@ int launch_stft_any(msd_stft_plan *plan, const void *x, int dtype, const int64_t
                     int64_t nfiles, void *out, int64_t ld);
 int launch_stft1024(msd_stft_plan *plan, const void *x, int dtype, const int64_t *off, const int64_t *len,
                     int64_t nfiles, float *out, int64_t ld);
+// block plans: L = min(block_size, n_fft) up to BLOCK_MAX_L; above BLOCK_FAST_MAX_L one 256-thread
+// workgroup per block (block_long_kernel), each lane a segment of block_long_spl(L) samples: L / 256
+// rounded up to a multiple of 8, so that a lane's segment starts on a 16-B boundary of an aligned
+// int16 block and is read in whole 8-sample chunks
+constexpr int BLOCK_FAST_MAX_L = 4096;
+constexpr int BLOCK_MAX_L = 65536;
+constexpr int block_long_spl(int L) { return ((L + 255) / 256 + 7) / 8 * 8; }
 bool block_i8_shape(int64_t L, int nbins);
 bool block_i8_window(const double *window, int64_t L);
 bool welch_i8_shape(const msd_welch_cfg &c, int nseg, int nslots, const double *window);

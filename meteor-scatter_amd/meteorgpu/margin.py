@@ -18,7 +18,9 @@ The bound (standard floating-point error model, u = 2^-53):
   Goertzel segments ``3 L_seg G + 24`` (L_seg = 16 ... 256 samples per lane, all of which a lane
   runs whatever L; G = min(1/|sin theta|, L_seg) the recurrence's error gain at bin angle theta,
   24 for the rotations and the 16-lane sum; the generic rotation kernel that takes plans above
-  64 bins runs half as many samples per lane and stays below that), or, for int16 blocks on
+  64 bins runs half as many samples per lane and stays below that; above 4096 samples a block is
+  spread over 256 lanes of L_seg = ceil(L / 256) rounded up to a multiple of 8, whose longer lane
+  sum makes it ``3 L_seg G + 28``), or, for int16 blocks on
   the exact integer path (csrc/block_i8.hip), ``10.25 L / sum(w)`` (its coefficients' 2^-55
   quantisation is absolute, not relative to the window) -- the larger of the two;
 * a band energy E = sum |X_k|^2 + 1e-12 over n bins then moves by at most
@@ -90,10 +92,22 @@ def _i8_chain(L: int, nbins: int, wsum: float) -> float:
     return 10.25 * float(L) / wsum if wsum > 0 else 0.0  # sum w = 0: every coefficient is 0, X = 0
 
 
+LONG_BLOCK = 4096  # above it one 256-lane workgroup takes a block (csrc/block_delta.hip block_long_kernel)
+
+
 def _block_spl(L: int) -> int:
     """samples per lane of the 16-lane Goertzel kernel (msd_block_plan_create): every lane runs all
-    of them, whatever L (a short or ragged block only zero-fills them)"""
+    of them, whatever L (a short or ragged block only zero-fills them).  Above 4096 samples the
+    256-lane kernel's: L / 256 rounded up to a multiple of 8 (csrc/msd_internal.h block_long_spl)."""
+    if L > LONG_BLOCK:
+        return ((int(L) + 255) // 256 + 7) // 8 * 8
     return 16 if L <= 256 else 32 if L <= 512 else 64 if L <= 1024 else 128 if L <= 2048 else 256
+
+
+def _long_chain(L: int, bins, nfft: int) -> float:
+    """3 SPL G + 28, the 256-lane kernel's counted chain: the Goertzel segments' 3 SPL G + 24, whose
+    lane sum is 4 adds, and the 4 further adds of 256 lanes (6 in the wave, 2 across the 4 waves)."""
+    return _goertzel_chain(_block_spl(int(L)), bins, nfft) + 4.0
 
 
 def _chain(nfft: int, L: int, bins: np.ndarray, wsum: float) -> float:
@@ -103,7 +117,10 @@ def _chain(nfft: int, L: int, bins: np.ndarray, wsum: float) -> float:
     kernel (csrc/block_delta.hip block_delta_kernel: above 64 bins or under MSD_OPT_GENERIC_STFT)
     runs half as many samples per lane; its chain, counted in tests/band_signals.py, is
     (3 sqrt 2 + 1) SPL / 2 + 11 - 2 sqrt 2 < 3 SPL + 24 at every L, so it needs no term here
-    (tests/test_band_signals.py holds that)."""
+    (tests/test_band_signals.py holds that).  Above 4096 samples one kernel runs whatever the bin
+    count or dtype: _long_chain."""
+    if int(L) > LONG_BLOCK:
+        return 4.0 * math.log2(nfft) + 8.0 + _long_chain(L, bins, nfft)
     dev = max(_goertzel_chain(_block_spl(int(L)), bins, nfft), _i8_chain(L, len(bins), wsum))
     return 4.0 * math.log2(nfft) + 8.0 + dev
 
