@@ -175,6 +175,10 @@ __global__ __launch_bounds__(F_NW * 64, 1) void stft1024_kernel(
     unsigned long long *__restrict__ ticket, float2 dcw0, float2 dcw1) {
     using IO = PairIO<T>;
     using raw_t = typename IO::raw_t;
+    // the transposes' LDS read bases held in 16 registers across the tile loop (read8 below) where that costs no
+    // scratch: int16 and the hop-512 uint8 form with 32-bit offsets (116-122 VGPRs).  The float32 forms, uint8 at
+    // other hops and every 64-bit-offset form sit at 118-128 VGPRs already and would spill 8-100 B
+    constexpr bool HOIST = (std::is_same_v<T, int16_t> || SH) && !WIDE;
     extern __shared__ __attribute__((aligned(16))) char smem[];
     float2 *buf = reinterpret_cast<float2 *>(smem);
     const int tid = threadIdx.x;
@@ -229,6 +233,38 @@ __global__ __launch_bounds__(F_NW * 64, 1) void stft1024_kernel(
             asm volatile("" : "+v"(ik));
             dst[k] = buf[ik];
             dst[k + 4] = buf[ik + 288];
+        }
+    };
+    // HOIST: the same four bases as opaque 32-bit LDS addresses (the x 8 included) made once, before the tile
+    // loop.  A read is then the ds_read_b64 alone; the opaque index above costs a v_mov, an s_nop and a
+    // v_lshl_add in front of every pair of reads in every iteration (32 VALU instructions and 16 nops per
+    // wave-iteration, eight of those chains right behind the tile barrier).  Measured -2.1 to -2.3 % on the C3
+    // launch (profiles/stft1024_barrier_window_ab.txt)
+    typedef float vf2 __attribute__((ext_vector_type(2)));
+    typedef __attribute__((address_space(3))) const vf2 lds_cf2;
+    struct Bases8 {
+        lds_cf2 *p[4];
+    };
+    auto bases8 = [&](int idx) {
+        Bases8 b;
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+            lds_cf2 *p = (lds_cf2 *)buf + (idx + 72 * k);
+            if constexpr (HOIST) asm volatile("" : "+v"(p));
+            b.p[k] = p;
+        }
+        return b;
+    };
+    auto get8 = [&](const Bases8 &b, int idx, float2 (&dst)[8]) {
+        if constexpr (HOIST) {
+#pragma unroll
+            for (int k = 0; k < 4; ++k) {
+                const vf2 lo = b.p[k][0], hi = b.p[k][288];
+                dst[k] = make_float2(lo.x, lo.y);
+                dst[k + 4] = make_float2(hi.x, hi.y);
+            }
+        } else {
+            read8(idx, dst);
         }
     };
     // the table entries as ds_read_b128 (two float2 each)
@@ -289,6 +325,8 @@ __global__ __launch_bounds__(F_NW * 64, 1) void stft1024_kernel(
     bool b_ok = cur.ti * F_TT + wcol + 1 < cur.nfr;  // the pair's second frame exists (wave-uniform)
     const float hs = vgpr_f(0.70710678118654752440f);  // sqrt(1/2) of the DFT8s, in a VGPR
     int tpar = 0;  // tile parity: the half of rbuf in use
+    const Bases8 bt0 = bases8(wave * F_PAIRF + rd[0]), bt1 = bases8(wave * F_PAIRF + F_SCRF + rd[1]);
+    const Bases8 b3a = bases8(i3a), b3b = bases8(i3b);
 
     for (int64_t tl = tb;;) {
         // the next tile: the next of this range, else (DYN) the first of the next drawn chunk
@@ -401,8 +439,8 @@ __global__ __launch_bounds__(F_NW * 64, 1) void stft1024_kernel(
                 make_float4(v[1][r + 1].x, v[1][r + 1].y, v[1][r].x, v[1][r].y);
         }
         wave_sync();
-        read8(wave * F_PAIRF + rd[0], v[0]);
-        read8(wave * F_PAIRF + F_SCRF + rd[1], v[1]);
+        get8(bt0, wave * F_PAIRF + rd[0], v[0]);
+        get8(bt1, wave * F_PAIRF + F_SCRF + rd[1], v[1]);
         wave_sync();
         // ---- pass 2 (Ns = 8): out[64 (l>>3) + (l&7) + 8 r]
         {
@@ -480,8 +518,8 @@ __global__ __launch_bounds__(F_NW * 64, 1) void stft1024_kernel(
             auto rowB_hi = [&](int h) { return SP && h == 0 ? 288 : 64 - 2 * wave - h; };
             const uint32_t offA_hi = offA + (s0 ? 32u : 256u) * ld4, offB_hi = offB + (s0 ? 224u * ld4 : 0u);
             float2 a[8], y[8];
-            read8(i3a, a);
-            read8(i3b, y);
+            get8(b3a, i3a, a);
+            get8(b3b, i3b, y);
             lds_barrier();  // every wave has read the tile's pass-2 output: the frame regions are free
             auto row4 = [](const float2 *p, int c) { return *reinterpret_cast<const float4 *>(p + c); };
             {
