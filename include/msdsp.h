@@ -229,7 +229,24 @@ typedef struct {
 } msd_hist_cfg;
 
 /* status word per file (device int32): 0 ok, 1 zero-duration global detection (reference
- * assert at main.py:437), 2 empty global input (IndexError at main.py:412), 3 capacity */
+ * assert at main.py:437), 2 empty global input (IndexError at main.py:412), 3 capacity
+ *
+ * Held bit for bit to the float64 numpy restatement of the reference over every file of a launch,
+ * whatever the other files are (tests/test_gpu_detect_contract.py):
+ *   - margin[f] is the minimum over all nblocks[f] blocks of |delta - threshold used| (adaptive:
+ *     the thresholds list's entry of that block; global: the single threshold), NaN terms
+ *     ignored, +inf if no term is left (no blocks, or a NaN threshold everywhere);
+ *   - delta columns at or past nblocks[f] are not read; thresholds is written at [0, nblocks[f])
+ *     of the row (global mode: entry 0 alone, NaN for an empty file);
+ *   - status 3 (more detections than cap): counts[f] is the full count and the first cap entries
+ *     are complete (start, stop, db); the histogram counts the stored detections only, i.e. the
+ *     first cap of that file.  Files within cap are unaffected;
+ *   - status 1 and 2 concern their own file only.  On status 1 the zero-duration detection is
+ *     counted and stored last (start = stop = nblocks[f] - 1, db = NaN);
+ *   - a block equal to its threshold is not above it (the reference's >);
+ *   - +inf, -inf and NaN blocks follow numpy's arithmetic as the reference would: a window or file
+ *     that holds one has a NaN threshold and nothing in it fires, a +inf block above a finite
+ *     threshold is a detection with db = +inf. */
 int msd_detect_dev(msd_ctx *ctx, const double *delta, const int64_t *nblocks, int64_t nfiles, int64_t ld,
                    const msd_det_cfg *cfg, msd_det *dets, int64_t cap, int64_t *counts, double *thresholds,
                    double *margin, int32_t *status, const msd_hist_cfg *hist);
