@@ -509,7 +509,28 @@ int msd_i8_coeffs(int kind, const double *window, int L, int nfft, int k, int pa
  *   (lock = thr + 0*std, start = block start, trigger block not in the history);
  *   Tracking appends over and ends when over < thr: emit if mean >= min_db and
  *   duration >= min_dur, then Detection(lock, until = block start + after_wait).
- * Block b starts at (b*block_size)/fs seconds. */
+ * Block b starts at (b*block_size)/fs seconds.
+ *
+ * Every output is bit-identical to the reference's float64, signs of zero included, and every
+ * comparison above is as strict as written (tests/live_cases.py):
+ *   times: t0 = (b*block_size)/fs and block end t1 = ((b+1)*block_size)/fs, each one integer
+ *   product divided once by fs, and until = t0 + after_wait, duration = t0 - start: separately
+ *   rounded doubles, never t0 + block_size/fs and never fused.  until and a later t1 are then a
+ *   rounding apart (fs 4000, block 800, wait 0.4 s: until > t1, < t1 and == t1 all occur), and a
+ *   lock holds one block longer or shorter by that rounding alone; equality means "run out", as
+ *   t0 == init_wait means "Init over" and duration == min_dur, mean == min_db mean "emit";
+ *   over: mean(n1, n2) is (0.0 + (n1 + n2)) / 2, numpy's reduction from +0.0: n1 = n2 = -0.0
+ *   gives +0.0;
+ *   non-finite rows: a band dB of -inf (digital silence), +inf or NaN propagates as in IEEE
+ *   arithmetic.  over = -inf or NaN never triggers and never ends Tracking by itself (NaN
+ *   compares false both ways; -inf < lock ends it); while such a value lies in the window the
+ *   fresh threshold is NaN and nothing triggers against it; a trigger under a lock then makes
+ *   lock + 0*std = NaN and that Tracking run never ends.  db_min / db_max are Python's
+ *   min / max over the history (the first element stays unless a later one compares strictly
+ *   below / above: a leading NaN stays, -0.0 before +0.0 stays); a NaN mean is never emitted;
+ *   buffers: thresholds / over are written at [f*ld, f*ld + nblocks[f]) only, out at
+ *   [f*cap, f*cap + min(counts[f], cap)) only, whatever ld and cap; band_db is read at
+ *   b < nblocks[f] only; cap = 0 and nblocks[f] = 0 are valid (count 0, status 0). */
 typedef struct {
     int32_t block_size;
     int32_t avg_win_blocks; /* int(avg_win_sec / proc_block_sec), processor.py:58 */

@@ -286,7 +286,7 @@ __global__ __launch_bounds__(WL_THREADS) void live_over_kernel(const double *__r
     const double *sig = band_db + (f * 3 + 0) * A.ld;
     const double *n1 = band_db + (f * 3 + 1) * A.ld;
     const double *n2 = band_db + (f * 3 + 2) * A.ld;
-    const double m = (-0.0 + n1[i] + n2[i]) / 2.0;
+    const double m = (0.0 + (-0.0 + n1[i] + n2[i])) / 2.0;  // np.add.reduce starts at +0.0 (np_reduce.h)
     over[f * A.ld + i] = sig[i] - m;
 }
 
@@ -630,7 +630,7 @@ __global__ __launch_bounds__(WL_THREADS) void live_session_over_kernel(const dou
     const double *sig = band_db + (f * 3 + 0) * ld;
     const double *n1 = band_db + (f * 3 + 1) * ld;
     const double *n2 = band_db + (f * 3 + 2) * ld;
-    const double m = (-0.0 + n1[i] + n2[i]) / 2.0;
+    const double m = (0.0 + (-0.0 + n1[i] + n2[i])) / 2.0;  // np.add.reduce starts at +0.0 (np_reduce.h)
     const double v = sig[i] - m;
     hist[f * A.hcap + st[f].retained + i] = v;  // retained <= H, i < P
     over[f * ld_over + i] = v;

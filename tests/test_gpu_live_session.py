@@ -11,6 +11,7 @@ import numpy as np
 import pytest
 
 from oracle import live_oracle as L
+from tests.live_cases import replay as _replay
 
 pytestmark = pytest.mark.gpu
 
@@ -39,24 +40,6 @@ def _random_rows(seed, nb=600):
     for s in rng.integers(50, nb - 10, 12):
         sig[s:s + rng.integers(1, 8)] += rng.uniform(5, 30)
     return np.stack([sig, rng.normal(0, 0.5, nb), rng.normal(0, 0.5, nb)])
-
-
-def _replay(thr, over, cfg):
-    """The oracle's state after each block, replayed from its thresholds used and over-noise values
-    (processor.py:448-504): ('init',) / ('detection', lock, until) / ('tracking', lock, t_start, trig)."""
-    state, out = ("init",), []
-    for b in range(len(over)):
-        t0 = (b * BS) / FS
-        if state[0] == "init":
-            if t0 >= cfg.init_detection_wait_sec:
-                state = ("detection", -1.0, -1.0)
-        elif state[0] == "detection":
-            if over[b] > thr[b]:
-                state = ("tracking", thr[b], t0, b)
-        elif over[b] < thr[b]:
-            state = ("detection", state[1], t0 + cfg.after_tracking_wait_sec)
-        out.append(state)
-    return out
 
 
 def _push_all(sess, rows, cuts):
