@@ -70,6 +70,9 @@ int msd_memset_dev(msd_ctx *ctx, void *dst, int value, size_t bytes);
 
 /* Options: MSD_OPT_GENERIC_STFT = 1 → use the generic STFT kernel even where a
  * specialised one exists (A/B testing of the kernels; results must agree).
+ * MSD_OPT_GENERIC_CSTFT = 1 → the I/Q spectrogram (msd_cstft_psd*) runs the generic kernel at nperseg =
+ * nfft = 4096 too, where the specialised one runs by default (A/B and tests; both within the per-bin
+ * bound, not bit-identical; msd_iq_band_delta_bound_dev then takes the larger of the two chains).
  * MSD_OPT_FRESH_ALL = 1 → the C5 stream detector computes every adaptive threshold exactly up
  * front instead of only where a scan reads it (A/B of that scheme; results must agree).
  * MSD_OPT_REFINE_GOERTZEL = 1 → msd_iq_delta64_dev computes int16 blocks with the float64
@@ -113,6 +116,7 @@ int msd_memset_dev(msd_ctx *ctx, void *dst, int value, size_t bytes);
 #define MSD_OPT_WELCH_GOERTZEL 9
 #define MSD_OPT_WELCH_I8_FORM 10
 #define MSD_OPT_STREAM_EPS_LOG2 11
+#define MSD_OPT_GENERIC_CSTFT 12
 int msd_set_option(msd_ctx *ctx, int option, int value);
 
 /* Per-kernel device timing with HIP events on the context stream.
@@ -256,16 +260,30 @@ int msd_detect(msd_ctx *ctx, const double *delta, int64_t nb, const msd_det_cfg 
                int64_t *count, double *thresholds, double *margin);
 
 /* --------------------------------------- C5: two-sided STFT of complex (I/Q) input
- * scipy.signal.spectrogram(z, fs, 'hann', nperseg=N, noverlap=N-hop) for complex z (BASELINE
- * config C5: 192 kHz I/Q, N = 4096, 75 % overlap): two-sided, bins in FFT order (0..N/2-1,
- * -N/2..-1), |X|^2 * scale, constant detrend of the complex frame mean, complex64 arithmetic.
- * window: N float32 (periodic Hann); scale = 1/(fs*sum(w^2)).  nperseg must be 4096.
- * Output FRAME-major: out[(s*max_frames + t)*N + k] (scipy's Sxx[k][t] transposed; a
+ * scipy.signal.spectrogram(z, fs, 'hann', nperseg, noverlap=nperseg-hop, nfft) for complex z (BASELINE
+ * config C5: 192 kHz I/Q, 4096-point frames, 75 % overlap): two-sided, bins in FFT order (0..nfft/2-1,
+ * -nfft/2..-1), |X|^2 * scale, no doubling, constant detrend of the complex mean of the nperseg samples
+ * (before the zero padding), zeros past nperseg, complex64 arithmetic.
+ * Shapes: any 1 <= nperseg <= nfft, nfft a power of two in [16, 8192], any 1 <= hop <= nperseg.  8192 is the
+ * real path's limit too (stft_any at nfft 16384 = 8192 complex points): above it MSD_ERR_UNSUPPORTED.
+ * nperseg = nfft = 4096 runs the kernel specialised to it, everything else the generic one
+ * (MSD_OPT_GENERIC_CSTFT: that one at 4096 too).  A stream shorter than nperseg has 0 frames.
+ * window: nperseg float32 (periodic Hann); scale = 1/(fs*sum(w^2)).  msd_cstft_plan_create is the
+ * nfft = nperseg case of msd_cstft_plan_create_ex; msd_cstft_nfft gives a plan's row length.
+ * Output FRAME-major: out[(s*max_frames + t)*nfft + k] (scipy's Sxx[k][t] transposed; a
  * frequency-major tile of 4096 rows would not fit in LDS); frames past a stream's end are 0.
- * off/len: device int64 arrays in complex samples; dtype MSD_CI16 or MSD_CF32. */
+ * off/len: device int64 arrays in complex samples; dtype MSD_CI16 or MSD_CF32.
+ * msd_cstft_chain (host only, no context): the rounding-chain constant c of the kernel that runs the
+ * shape -- every bin's amplitude is within c * 2^-24 * sqrt(sum_k out[k]) (+ 3 * 2^-24 of itself) of the
+ * float64 reference's: 37 at 4096 / 4096, else the generic kernel's count of its passes
+ * (csrc/cstft_chain.h). */
 typedef struct msd_cstft_plan msd_cstft_plan;
 int msd_cstft_plan_create(msd_ctx *ctx, int32_t nperseg, int32_t hop, const float *window, double scale,
                           msd_cstft_plan **out);
+int msd_cstft_plan_create_ex(msd_ctx *ctx, int32_t nperseg, int32_t nfft, int32_t hop, const float *window,
+                             double scale, msd_cstft_plan **out);
+int32_t msd_cstft_nfft(const msd_cstft_plan *plan);
+int msd_cstft_chain(int32_t nperseg, int32_t nfft, double *chain);
 void msd_cstft_plan_destroy(msd_cstft_plan *plan);
 int msd_cstft_set_detrend(msd_cstft_plan *plan, int detrend);
 int64_t msd_cstft_frames(const msd_cstft_plan *plan, int64_t n);
@@ -281,15 +299,15 @@ int msd_cstft_psd_energy_dev(msd_cstft_plan *plan, const void *x, int dtype, con
                              int64_t nstreams, int64_t max_frames, float *out, float *etot);
 /* the same, with each frame's complex sample sum given (frame_sums: device double [nstreams *
  * max_frames][2], (sum I, sum Q) of frame s*max_frames + t, e.g. from msd_iq_delta64_sums_dev):
- * at the C5 hop (1024) the kernel then takes each frame's detrend mean from these sums and computes
- * none itself; other hops ignore them.  Exact sums (int16 input) give output bit-identical to
+ * at the C5 shape (4096 / 4096, hop 1024) the kernel then takes each frame's detrend mean from these sums
+ * and computes none itself; other hops and the generic kernel ignore them.  Exact sums (int16 input) give output bit-identical to
  * msd_cstft_psd_energy_dev.  Either way the mean is subtracted before the window as an exact
  * two-part float32 value (hi + lo), so the result is scipy's within float32 rounding of the
  * detrended samples whatever the DC offset. */
 int msd_cstft_psd_fsums_dev(msd_cstft_plan *plan, const void *x, int dtype, const int64_t *off, const int64_t *len,
                             int64_t nstreams, int64_t max_frames, float *out, float *etot, const double *frame_sums);
 int64_t msd_cstft_energy_stride(int64_t nstreams, int64_t max_frames);
-/* one stream, host buffers: n complex samples in, out float32 [T][N] */
+/* one stream, host buffers: n complex samples in, out float32 [T][nfft] */
 int msd_cstft_psd(msd_cstft_plan *plan, const void *x, int dtype, int64_t n, float *out, int64_t *frames);
 
 /* -------------------------------- C5: band / noise dB per frame of the I/Q spectrogram
@@ -307,7 +325,10 @@ int msd_iq_band_delta_dev(msd_ctx *ctx, const float *spec, int64_t nstreams, int
 /* the same plus ed[s*ld + t] (device float64): a bound on |delta - delta_ref| against the float64
  * reference (scipy's spectrogram of complex128 input, its band sums and dB), from the standard
  * rounding-error model of the fp32 FFT and the frame energies etot of msd_cstft_psd_energy_dev
- * (stream.hip IQ_CHAIN); +inf where a band touches bins -1..1 (the detrend's DC term). */
+ * (stream.hip IQ_CHAIN; the chain is msd_cstft_chain's for rows of nperseg floats); +inf where a band
+ * touches bins -1..1 (the detrend's DC term).  Rows of a zero-padded plan (nfft > nperseg) are not
+ * covered: there the mean's rounding leaks past bins -1..1 (the window's transform is no longer compact
+ * on the finer grid), so certification is limited to nfft = nperseg. */
 int msd_iq_band_delta_bound_dev(msd_ctx *ctx, const float *spec, const float *etot, int64_t nstreams,
                                 int64_t max_frames, const int64_t *frames, int32_t nperseg, int32_t band_lo,
                                 int32_t band_hi, int32_t noise_lo, int32_t noise_hi, double *band_db, double *noise_db,

@@ -16,11 +16,14 @@
 // consecutive bins per instruction, no output tile.  (A frequency-major [K][T] tile for
 // K = 4096 would need 512 KB of LDS per 128-B row segment; scipy's [K][T] is the transpose of
 // this layout.)  The window carries sqrt(scale), so |X|^2 is the density directly.
+// Every other shape (nperseg != nfft, nfft = 16 .. 8192 but 4096; 4096 under MSD_OPT_GENERIC_CSTFT) runs
+// cstft_any_kernel (cstft_any.hip); the plan functions below serve both.
 #include <algorithm>
 #include <cmath>
 #include <cstddef>
 #include <type_traits>
 
+#include "cstft_chain.h"
 #include "fft_butterfly.h"
 #include "msd_internal.h"
 
@@ -360,45 +363,43 @@ __global__ __launch_bounds__(CS_T, (CsTune<T, SH>::kWavesPerSimd)) void cstft409
 }  // namespace
 }  // namespace msd
 
-struct msd_cstft_plan {
-    msd_ctx *ctx = nullptr;
-    int nperseg = 0, hop = 0, detrend = 1;
-    float *d_win = nullptr;   // window x sqrt(scale)
-    float2 *d_tw = nullptr;   // W4096^m, m = 0..4095
-    // DYN: the guided chunk schedule for (sched_total frames, sched_wgs workgroups) and the ticket
-    int64_t *d_sched = nullptr;
-    int64_t sched_cap = 0, sched_total = -1, sched_wgs = -1, sched_n = 0;
-    unsigned long long *d_ticket = nullptr;
-};
-
 using namespace msd;
 
 extern "C" {
 
 int msd_cstft_plan_create(msd_ctx *ctx, int32_t nperseg, int32_t hop, const float *window, double scale,
                           msd_cstft_plan **out) {
+    return msd_cstft_plan_create_ex(ctx, nperseg, nperseg, hop, window, scale, out);
+}
+
+int msd_cstft_plan_create_ex(msd_ctx *ctx, int32_t nperseg, int32_t nfft, int32_t hop, const float *window,
+                             double scale, msd_cstft_plan **out) {
     if (!ctx || !window || !out) return fail(MSD_ERR_INVALID, "msd_cstft_plan_create: null");
     *out = nullptr;
-    if (nperseg != CS_N) return fail(MSD_ERR_UNSUPPORTED, "cstft: nperseg must be 4096");
+    if (nfft > (1 << CSA_MAX_LOG2))
+        return fail(MSD_ERR_UNSUPPORTED, "cstft: nfft above 8192 (8192 complex points fill one workgroup's LDS)");
+    if (csa_log2(nfft) < 0) return fail(MSD_ERR_UNSUPPORTED, "cstft: nfft must be a power of two in [16, 8192]");
+    if (nperseg < 1 || nperseg > nfft) return fail(MSD_ERR_INVALID, "cstft: need 1 <= nperseg <= nfft");
     if (hop <= 0 || hop > nperseg) return fail(MSD_ERR_INVALID, "cstft: need 0 < hop <= nperseg");
     if (!(scale > 0)) return fail(MSD_ERR_INVALID, "cstft: scale must be > 0");
     DeviceGuard g(ctx->device);
     auto *p = new msd_cstft_plan();
     p->ctx = ctx;
     p->nperseg = nperseg;
+    p->nfft = nfft;
     p->hop = hop;
     std::vector<float> w(nperseg);
     const double rs = std::sqrt(scale);
     for (int i = 0; i < nperseg; ++i) w[i] = (float)((double)window[i] * rs);
-    std::vector<float2> tw(CS_N);
-    for (int m = 0; m < CS_N; ++m) {
-        const double a = -2.0 * M_PI * (double)m / (double)CS_N;
+    std::vector<float2> tw(nfft);
+    for (int m = 0; m < nfft; ++m) {
+        const double a = -2.0 * M_PI * (double)m / (double)nfft;
         tw[m] = make_float2((float)std::cos(a), (float)std::sin(a));
     }
     hipError_t e = hipMalloc(&p->d_win, sizeof(float) * nperseg);
-    if (e == hipSuccess) e = hipMalloc(&p->d_tw, sizeof(float2) * CS_N);
+    if (e == hipSuccess) e = hipMalloc(&p->d_tw, sizeof(float2) * nfft);
     if (e == hipSuccess) e = hipMemcpy(p->d_win, w.data(), sizeof(float) * nperseg, hipMemcpyHostToDevice);
-    if (e == hipSuccess) e = hipMemcpy(p->d_tw, tw.data(), sizeof(float2) * CS_N, hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = hipMemcpy(p->d_tw, tw.data(), sizeof(float2) * nfft, hipMemcpyHostToDevice);
     if (e != hipSuccess) {
         msd_cstft_plan_destroy(p);
         return hip_fail(e, "msd_cstft_plan_create");
@@ -429,6 +430,8 @@ int64_t msd_cstft_frames(const msd_cstft_plan *p, int64_t n) {
     return (n - p->nperseg) / p->hop + 1;
 }
 
+int32_t msd_cstft_nfft(const msd_cstft_plan *p) { return p ? p->nfft : 0; }
+
 int msd_cstft_psd_dev(msd_cstft_plan *p, const void *x, int dtype, const int64_t *off, const int64_t *len,
                       int64_t nstreams, int64_t max_frames, float *out) {
     return msd_cstft_psd_energy_dev(p, x, dtype, off, len, nstreams, max_frames, out, nullptr);
@@ -448,6 +451,9 @@ int msd_cstft_psd_fsums_dev(msd_cstft_plan *p, const void *x, int dtype, const i
     if (dtype != MSD_CI16 && dtype != MSD_CF32) return fail(MSD_ERR_UNSUPPORTED, "cstft: dtype must be CI16 or CF32");
     if (nstreams == 0 || max_frames == 0) return MSD_OK;
     DeviceGuard g(p->ctx->device);
+    // cstft4096_kernel serves nperseg = nfft = 4096 (unless MSD_OPT_GENERIC_CSTFT); cstft_any_kernel the rest
+    if (p->nperseg != CS_N || p->nfft != CS_N || p->ctx->force_generic_cstft)
+        return launch_cstft_any(p, x, dtype, off, len, nstreams, max_frames, out, etot);
     const int64_t total = nstreams * max_frames;
     // persistent: as many workgroups as stay resident (registers and the 37 KB of LDS decide; the
     // compiler's register count sets 3 or 4 per CU), less the reserve
@@ -552,14 +558,14 @@ int msd_cstft_psd(msd_cstft_plan *p, const void *x, int dtype, int64_t n, float 
     int rc;
     if ((rc = ctx_scratch(ctx, 0, ((size_t)n * es + 255) / 256 * 256, &dx))) return rc;
     if ((rc = ctx_scratch(ctx, 1, 64, &dmeta))) return rc;
-    if ((rc = ctx_scratch(ctx, 2, sizeof(float) * CS_N * (size_t)T, &dout))) return rc;
+    if ((rc = ctx_scratch(ctx, 2, sizeof(float) * (size_t)p->nfft * (size_t)T, &dout))) return rc;
     int64_t meta[2] = {0, n};
     MSD_HIP(hipMemcpyAsync(dx, x, (size_t)n * es, hipMemcpyHostToDevice, ctx->stream));
     MSD_HIP(hipMemcpyAsync(dmeta, meta, sizeof(meta), hipMemcpyHostToDevice, ctx->stream));
     const int64_t *doff = static_cast<const int64_t *>(dmeta);
     rc = msd_cstft_psd_dev(p, dx, dtype, doff, doff + 1, 1, T, static_cast<float *>(dout));
     if (rc) return rc;
-    MSD_HIP(hipMemcpyAsync(out, dout, sizeof(float) * CS_N * (size_t)T, hipMemcpyDeviceToHost, ctx->stream));
+    MSD_HIP(hipMemcpyAsync(out, dout, sizeof(float) * (size_t)p->nfft * (size_t)T, hipMemcpyDeviceToHost, ctx->stream));
     MSD_HIP(hipStreamSynchronize(ctx->stream));
     return MSD_OK;
 }

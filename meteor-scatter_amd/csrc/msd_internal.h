@@ -44,6 +44,7 @@ struct msd_ctx {
     bool timing = false;
     uint32_t timing_mask = 0xffffffffu;  // msd_timing_select: kernel ids timed while timing is on
     bool force_generic = false;  // MSD_OPT_GENERIC_STFT
+    bool force_generic_cstft = false;  // MSD_OPT_GENERIC_CSTFT
     bool fresh_all = false;      // MSD_OPT_FRESH_ALL
     std::vector<msd::EventPair> pending;  // recorded, not yet folded into totals
     std::vector<hipEvent_t> pool;         // reusable events
@@ -108,6 +109,17 @@ struct msd_stft_plan {
     // 1e-6 |W_0| (else integer input takes the generic kernel's exact two-part mean)
     double2 win_dft01[2] = {};
     int win_dft_compact = 0;
+};
+
+struct msd_cstft_plan {
+    msd_ctx *ctx = nullptr;
+    int nperseg = 0, nfft = 0, hop = 0, detrend = 1;
+    float *d_win = nullptr;   // [nperseg] window x sqrt(scale)
+    float2 *d_tw = nullptr;   // [nfft] W_nfft^m
+    // cstft4096_kernel, DYN: the guided chunk schedule for (sched_total frames, sched_wgs workgroups) and the ticket
+    int64_t *d_sched = nullptr;
+    int64_t sched_cap = 0, sched_total = -1, sched_wgs = -1, sched_n = 0;
+    unsigned long long *d_ticket = nullptr;
 };
 
 struct msd_block_plan {
@@ -281,6 +293,9 @@ int launch_stft_any(msd_stft_plan *plan, const void *x, int dtype, const int64_t
                     int64_t nfiles, void *out, int64_t ld);
 int launch_stft1024(msd_stft_plan *plan, const void *x, int dtype, const int64_t *off, const int64_t *len,
                     int64_t nfiles, float *out, int64_t ld);
+// every I/Q spectrogram shape but nperseg = nfft = 4096 (cstft_any.hip); frame_sums are not used
+int launch_cstft_any(msd_cstft_plan *plan, const void *x, int dtype, const int64_t *off, const int64_t *len,
+                     int64_t nstreams, int64_t max_frames, float *out, float *etot);
 // block plans: L = min(block_size, n_fft) up to BLOCK_MAX_L; above BLOCK_FAST_MAX_L one 256-thread
 // workgroup per block (block_long_kernel), each lane a segment of block_long_spl(L) samples: L / 256
 // rounded up to a multiple of 8, so that a lane's segment starts on a 16-B boundary of an aligned

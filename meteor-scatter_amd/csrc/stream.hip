@@ -27,6 +27,7 @@
 //                          fixed point (normally 2 rounds: speculative clean start, then fix-up)
 //   runs_kernel, db_kernel the shard's runs (merged over segment edges) and np.mean dB of each
 // FP contraction is off: numpy rounds every add / multiply separately.
+#include "cstft_chain.h"
 #include "msd_internal.h"
 #include "np_program.h"
 #include "np_reduce.h"
@@ -140,6 +141,9 @@ struct PinHdr {  // head of msd_stream_plan::h_pin, then margins [nseg], then ch
 // (unbounded once dE >= E); delta by the sum of the two bands'.  A band touching bins -1..1 also
 // carries the frame mean's rounding (the DC offset's transform): not bounded here, +inf.
 constexpr double IQ_CHAIN = 37.0;
+// the other frame lengths (cstft_any_kernel) carry the count of their own passes, cstft_chain.h, which the
+// host hands to iq_band_delta_kernel as `chain`; N is then the row length nfft = nperseg
+static_assert(IQ_CHAIN == CSTFT4096_CHAIN, "cstft_chain.h restates cstft4096_kernel's count");
 
 __device__ __forceinline__ double band_db_bound(double E, int n, double d) {
     if (n <= 0) return 0.0;  // empty band: 1e-12 on both sides
@@ -188,7 +192,8 @@ __global__ __launch_bounds__(256) void iq_band_delta_kernel(const float *__restr
                                                             double *__restrict__ band_db,
                                                             double *__restrict__ noise_db,
                                                             double *__restrict__ delta, int64_t ld,
-                                                            const float *__restrict__ etot, double *__restrict__ ed) {
+                                                            const float *__restrict__ etot, double *__restrict__ ed,
+                                                            double chain) {
     const int64_t g = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (g >= nstreams * max_frames) return;
     const int64_t s = g / max_frames, t = g - s * max_frames;
@@ -206,7 +211,7 @@ __global__ __launch_bounds__(256) void iq_band_delta_kernel(const float *__restr
         for (int q = 0; q < 16; ++q) S += (double)__builtin_nontemporal_load(etot + q * es + s * max_frames + t);
         const double A = sqrt(S * 1.001);
         const double lg = log2((double)N);
-        const double d = IQ_CHAIN * 0x1p-24 * A + (4.0 * lg + 11.0) * 0x1p-53 * sqrt((double)N) * A;
+        const double d = chain * 0x1p-24 * A + (4.0 * lg + 11.0) * 0x1p-53 * sqrt((double)N) * A;
         double b = band_db_bound(e0, bhi - blo + 1, d) + band_db_bound(e1, nhi - nlo + 1, d);
         if (near_dc(blo, bhi) || near_dc(nlo, nhi) || !(S >= 0.0)) b = __builtin_inf();
         ed[s * ld + t] = b + 1e-12;
@@ -1230,11 +1235,15 @@ int msd_iq_band_delta_bound_dev(msd_ctx *ctx, const float *spec, const float *et
         return fail(MSD_ERR_INVALID, "msd_iq_band_delta_dev: band outside -N/2 .. N/2-1");
     if (nstreams == 0 || max_frames == 0) return MSD_OK;
     DeviceGuard g(ctx->device);
+    // the chain of the kernel that wrote rows of this length (cstft_chain.h; IQ_CHAIN = cstft4096_kernel's
+    // at 4096, also for a row length no spectrogram kernel writes)
+    double chain = cstft_row_chain(nperseg, ctx->force_generic_cstft);
+    if (!(chain > 0.0)) chain = IQ_CHAIN;
     KernelTimer timer(ctx, K_IQDELTA);
     const int64_t blocks = (nstreams * max_frames + 255) / 256;
     hipLaunchKernelGGL(iq_band_delta_kernel, dim3((unsigned)blocks), dim3(256), 0, ctx->stream, spec, nstreams,
                        max_frames, frames, (int)nperseg, band_lo, band_hi, noise_lo, noise_hi, band_db, noise_db,
-                       delta, ld, etot, ed);
+                       delta, ld, etot, ed, chain);
     MSD_HIP(hipGetLastError());
     return MSD_OK;
 }

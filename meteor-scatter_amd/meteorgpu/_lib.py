@@ -47,6 +47,7 @@ OPT_BLOCK_GOERTZEL = 8
 OPT_WELCH_GOERTZEL = 9
 OPT_WELCH_I8_FORM = 10     # test hook: bit 0 no int32 pairs, bit 1 the generic instantiation
 OPT_STREAM_EPS_LOG2 = 11   # test hook: the stream detector's near-tie bound times 2^n
+OPT_GENERIC_CSTFT = 12     # the generic I/Q spectrogram kernel at 4096 / 4096 too (A/B, tests)
 COMM_ID_BYTES = 128
 
 
@@ -205,6 +206,9 @@ _SIGS = [
     ("msd_detect", C.c_int,
      [_P, _P, C.c_int64, C.POINTER(MsdDetCfg), _P, C.c_int64, C.POINTER(C.c_int64), _P, _P]),
     ("msd_cstft_plan_create", C.c_int, [_P, C.c_int32, C.c_int32, _P, C.c_double, C.POINTER(_P)]),
+    ("msd_cstft_plan_create_ex", C.c_int, [_P, C.c_int32, C.c_int32, C.c_int32, _P, C.c_double, C.POINTER(_P)]),
+    ("msd_cstft_nfft", C.c_int32, [_P]),
+    ("msd_cstft_chain", C.c_int, [C.c_int32, C.c_int32, C.POINTER(C.c_double)]),
     ("msd_cstft_plan_destroy", None, [_P]),
     ("msd_cstft_set_detrend", C.c_int, [_P, C.c_int]),
     ("msd_cstft_frames", C.c_int64, [_P, C.c_int64]),
@@ -660,18 +664,30 @@ def live_detect(ctx: Context, band_db: np.ndarray, cfg: MsdLiveCfg, cap: int | N
     return out[: count.value], thr[:nb], over[:nb]
 
 
+def cstft_chain(nperseg: int, nfft: int | None = None) -> float:
+    """msd_cstft_chain: the rounding-chain constant of the I/Q spectrogram kernel that runs the shape
+    (host only)."""
+    v = C.c_double(0.0)
+    check(load().msd_cstft_chain(int(nperseg), int(nperseg if nfft is None else nfft), C.byref(v)))
+    return v.value
+
+
 class CStftPlan:
     """Two-sided power spectrogram of complex (I/Q) samples (include/msdsp.h, config C5)."""
 
-    def __init__(self, ctx: Context, nperseg: int, hop: int, window: np.ndarray, scale: float):
+    def __init__(self, ctx: Context, nperseg: int, hop: int, window: np.ndarray, scale: float,
+                 nfft: int | None = None):
         self.ctx = ctx
         w = np.ascontiguousarray(window, dtype=np.float32)
         if w.shape != (nperseg,):
             raise ValueError("window length must equal nperseg")
+        nfft = int(nperseg) if nfft is None else int(nfft)
         h = C.c_void_p()
-        check(ctx.lib.msd_cstft_plan_create(ctx.h, int(nperseg), int(hop), ptr(w), float(scale), C.byref(h)))
+        check(ctx.lib.msd_cstft_plan_create_ex(ctx.h, int(nperseg), nfft, int(hop), ptr(w), float(scale),
+                                               C.byref(h)))
         self.h = h
         self.nperseg, self.hop = int(nperseg), int(hop)
+        self.nfft = int(ctx.lib.msd_cstft_nfft(h))
 
     def close(self):
         if getattr(self, "h", None) and self.ctx.h:  # a plan outliving its context leaks, never crashes
@@ -688,11 +704,11 @@ class CStftPlan:
         return int(self.ctx.lib.msd_cstft_frames(self.h, int(n)))
 
     def run(self, iq: np.ndarray, dtype_code_iq: int) -> np.ndarray:
-        """iq: interleaved I/Q (int16 or float32), 2*n elements → float32 [T][nperseg] (frame-major)."""
+        """iq: interleaved I/Q (int16 or float32), 2*n elements → float32 [T][nfft] (frame-major)."""
         iq = np.ascontiguousarray(iq)
         n = iq.shape[0] // 2
         T = self.frames(n)
-        out = np.empty((T, self.nperseg), np.float32)
+        out = np.empty((T, self.nfft), np.float32)
         t = C.c_int64(0)
         check(self.ctx.lib.msd_cstft_psd(self.h, ptr(iq), int(dtype_code_iq), int(n), ptr(out), C.byref(t)))
         return out

@@ -21,10 +21,10 @@ from . import stream as _stream
 from .dsp import OutputDetection, _blocks, _utc, context, hann_periodic, write_csv
 
 
-def _plan(ctx, fs, nperseg, noverlap):
+def _plan(ctx, fs, nperseg, noverlap, nfft=None):
     w = hann_periodic(nperseg).astype(np.complex64)      # scipy casts the window to complex64
     scale = float(np.real(1.0 / (fs * (w * w).sum())))
-    return _lib.CStftPlan(ctx, nperseg, nperseg - noverlap, w.real.astype(np.float32), scale)
+    return _lib.CStftPlan(ctx, nperseg, nperseg - noverlap, w.real.astype(np.float32), scale, nfft)
 
 
 def interleave(i: np.ndarray, q: np.ndarray) -> tuple[np.ndarray, int]:
@@ -42,18 +42,22 @@ def interleave(i: np.ndarray, q: np.ndarray) -> tuple[np.ndarray, int]:
     return out, code
 
 
-def spectrogram_iq(i, q, fs, nperseg=4096, noverlap=None, device: int = 0):
-    """scipy.signal.spectrogram(i + 1j*q, fs, 'hann', nperseg, noverlap) → (f, t, Sxx[N][T])."""
+def spectrogram_iq(i, q, fs, nperseg=4096, noverlap=None, device: int = 0, *, nfft=None):
+    """scipy.signal.spectrogram(i + 1j*q, fs, 'hann', nperseg, noverlap, nfft) → (f, t, Sxx[nfft][T]).
+    Any 1 <= nperseg <= nfft, nfft (default nperseg) a power of two in [16, 8192], any noverlap < nperseg.
+    An input shorter than nperseg gives 0 frames: scipy's shrinking of nperseg to the input length (a
+    frame length that is no power of two) is out of scope."""
     if noverlap is None:
         noverlap = nperseg // 8  # scipy's default
     buf, code = interleave(i, q)
-    plan = _plan(context(device), fs, nperseg, noverlap)
+    plan = _plan(context(device), fs, nperseg, noverlap, nfft)
+    nfft = plan.nfft
     try:
         S = plan.run(buf, code)
     finally:
         plan.close()
     n = buf.size // 2
-    f = np.fft.fftfreq(nperseg, 1 / fs)
+    f = np.fft.fftfreq(nfft, 1 / fs)
     t = np.arange(nperseg / 2, n - nperseg / 2 + 1, nperseg - noverlap) / float(fs)
     return f, t, S.T
 
@@ -63,12 +67,12 @@ class IQBatch:
     HBM: x [nstreams][2 n_pad] elements, out float32 [nstreams][T][N] (frame-major)."""
 
     def __init__(self, ctx: _lib.Context, nstreams: int, n_per_stream: int, fs, nperseg=4096, noverlap=3072,
-                 dtype=np.int16):
+                 dtype=np.int16, nfft=None):
         self.ctx, self.ns, self.n = ctx, int(nstreams), int(n_per_stream)
         self.dtype = np.dtype(dtype)
         self.code = _lib.MSD_CI16 if self.dtype == np.int16 else _lib.MSD_CF32
-        self.plan = _plan(ctx, fs, nperseg, noverlap)
-        self.N = int(nperseg)
+        self.plan = _plan(ctx, fs, nperseg, noverlap, nfft)
+        self.N = self.plan.nfft  # row length
         self.T = self.plan.frames(self.n)
         self.n_pad = (self.n + 3) // 4 * 4
         es = self.dtype.itemsize
@@ -208,6 +212,10 @@ class IQShardDetector(_stream.CertifyingShard):
     def _init(self, ctx, fs, noverlap, freq_band, noise_band, threshold_std_factor, nb, dtype, delta, seg_len,
               certify, Fa, Fb):
         self.batch = IQBatch(self.sctx, 1, nb, fs, self.N, noverlap, dtype)
+        if self.batch.plan.nfft != self.N:
+            # the bands, the error bound (near_dc: bins -1..1 only) and the float64 refinement are those
+            # of rows of nperseg bins: certification is limited to nfft = nperseg (include/msdsp.h)
+            raise ValueError("IQShardDetector needs a spectrogram plan with nfft == nperseg (no zero padding)")
         if delta not in ("auto", "fp32", "exact"):
             raise ValueError(f"delta must be 'auto', 'fp32' or 'exact', not {delta!r}")
         try:
