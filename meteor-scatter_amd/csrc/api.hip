@@ -13,6 +13,7 @@
 
 #include <vector>
 
+#include "guided_sched.h"
 #include "msd_internal.h"
 
 namespace msd {
@@ -65,20 +66,41 @@ KernelTimer::~KernelTimer() {
     ctx->pending.push_back({a, b, kernel});
 }
 
-int ctx_scratch(msd_ctx *ctx, int slot, size_t bytes, void **out) {
-    if (ctx->scratch_bytes[slot] < bytes) {
-        if (ctx->scratch[slot]) {
-            MSD_HIP(hipStreamSynchronize(ctx->stream));
-            MSD_HIP(hipFree(ctx->scratch[slot]));
-            ctx->scratch[slot] = nullptr;
-            ctx->scratch_bytes[slot] = 0;
-        }
-        size_t want = bytes < 4096 ? 4096 : bytes;
-        ctx->rf_last_dev = nullptr;  // a new block (perhaps at the old address) holds no uploaded tables
-        MSD_HIP(hipMalloc(&ctx->scratch[slot], want));
-        ctx->scratch_bytes[slot] = want;
+int ctx_scratch(msd_ctx *ctx, ScratchSlot slot, size_t bytes, void **out) {
+    if (int rc = ctx->scratch[slot].grow(bytes < 4096 ? 4096 : bytes, ctx->stream, "ctx_scratch")) return rc;
+    *out = ctx->scratch[slot].get();
+    return MSD_OK;
+}
+
+int stage_one_file(msd_ctx *ctx, const void *x, size_t bytes, int64_t n, const void **dx, const int64_t **doff) {
+    void *ds, *dmeta;
+    if (int rc = ctx_scratch(ctx, SCRATCH_SAMPLES, (bytes + 255) / 256 * 256, &ds)) return rc;
+    if (int rc = ctx_scratch(ctx, SCRATCH_META, 64, &dmeta)) return rc;
+    ctx->file_meta[0] = 0;
+    ctx->file_meta[1] = n;
+    MSD_HIP(hipMemcpyAsync(ds, x, bytes, hipMemcpyHostToDevice, ctx->stream));
+    MSD_HIP(hipMemcpyAsync(dmeta, ctx->file_meta, sizeof(ctx->file_meta), hipMemcpyHostToDevice, ctx->stream));
+    *dx = ds;
+    *doff = static_cast<const int64_t *>(dmeta);
+    return MSD_OK;
+}
+
+int guided_sched_prepare(GuidedSched &s, hipStream_t stream, int64_t total, int64_t wgs, int64_t div, int64_t cmin,
+                         int64_t multiple, bool merge_short_tail) {
+    if (s.total != total || s.wgs != wgs) {
+        std::vector<int64_t> st;
+        guided_chunks(total, wgs, div, cmin, multiple, merge_short_tail, st);
+        MSD_HIP(hipStreamSynchronize(stream));  // the last launch still reads the old schedule
+        if (s.bounds.size() < st.size())
+            if (int rc = s.bounds.alloc(st.size(), "guided schedule")) return rc;
+        if (!s.ticket.get())
+            if (int rc = s.ticket.alloc(1, "guided schedule ticket")) return rc;
+        MSD_HIP(hipMemcpy(s.bounds.get(), st.data(), sizeof(int64_t) * st.size(), hipMemcpyHostToDevice));
+        s.total = total;
+        s.wgs = wgs;
+        s.n = (int64_t)st.size() - 1;
     }
-    *out = ctx->scratch[slot];
+    MSD_HIP(hipMemsetAsync(s.ticket.get(), 0, sizeof(unsigned long long), stream));
     return MSD_OK;
 }
 
@@ -180,12 +202,6 @@ void msd_destroy(msd_ctx *ctx) {
         hipEventDestroy(p.b);
     }
     for (auto e : ctx->pool) hipEventDestroy(e);
-    for (void *p : ctx->scratch)
-        if (p) hipFree(p);
-    if (ctx->rf_w) hipFree(ctx->rf_w);
-    if (ctx->rf_ev) hipEventSynchronize(ctx->rf_ev), hipEventDestroy(ctx->rf_ev);
-    if (ctx->rf_pin) hipHostFree(ctx->rf_pin);
-    if (ctx->i8_tab) hipFree(ctx->i8_tab);
     if (ctx->copy_stream) {
         hipStreamSynchronize(ctx->copy_stream);
         hipStreamDestroy(ctx->copy_stream);
@@ -367,7 +383,7 @@ int stft_plan_make(msd_ctx *ctx, int32_t nperseg, int32_t nfft, int32_t hop, con
     if (hop <= 0) return fail(MSD_ERR_INVALID, "stft: need hop = nperseg - noverlap > 0");
     if (precision != MSD_F32 && precision != MSD_F64) return fail(MSD_ERR_INVALID, "stft: precision must be F32 or F64");
     DeviceGuard g(ctx->device);
-    auto *p = new msd_stft_plan();
+    auto p = std::make_unique<msd_stft_plan>();
     p->ctx = ctx;
     p->nperseg = nperseg;
     p->nfft = nfft;
@@ -385,7 +401,7 @@ int stft_plan_make(msd_ctx *ctx, int32_t nperseg, int32_t nfft, int32_t hop, con
         const double a = -M_PI * (double)k / (double)M;
         post[k] = make_double2(std::cos(a), std::sin(a));
     }
-    hipError_t e = hipSuccess;
+    int rc;
     if (precision == MSD_F32) {
         std::vector<float2> tw32(M), post32(M + 1);
         for (int m = 0; m < M; ++m) tw32[m] = make_float2((float)tw[m].x, (float)tw[m].y);
@@ -412,27 +428,18 @@ int stft_plan_make(msd_ctx *ctx, int32_t nperseg, int32_t nfft, int32_t hop, con
             const double w0 = std::hypot(p->win_dft01[0].x, p->win_dft01[0].y);
             p->win_dft_compact = w0 > 0.0 && wmax <= 1e-6 * w0;
         }
-        e = hipMalloc(&p->d_window, sizeof(float) * nperseg);
-        if (e == hipSuccess) e = hipMalloc(&p->d_tw, sizeof(float2) * M);
-        if (e == hipSuccess) e = hipMalloc(&p->d_post, sizeof(float2) * (M + 1));
-        if (e == hipSuccess) e = hipMemcpy(p->d_window, win.data(), sizeof(float) * nperseg, hipMemcpyHostToDevice);
-        if (e == hipSuccess) e = hipMemcpy(p->d_tw, tw32.data(), sizeof(float2) * M, hipMemcpyHostToDevice);
-        if (e == hipSuccess) e = hipMemcpy(p->d_post, post32.data(), sizeof(float2) * (M + 1), hipMemcpyHostToDevice);
+        (rc = p->d_window.upload(win.data(), nperseg, "stft plan upload")) ||
+            (rc = p->d_tw.upload(tw32.data(), M, "stft plan upload")) ||
+            (rc = p->d_post.upload(post32.data(), M + 1, "stft plan upload"));
     } else {
         std::vector<double> win(nperseg);
         for (int i = 0; i < nperseg; ++i) win[i] = w64 ? w64[i] : (double)w32[i];
-        e = hipMalloc(&p->d_window64, sizeof(double) * nperseg);
-        if (e == hipSuccess) e = hipMalloc(&p->d_tw64, sizeof(double2) * M);
-        if (e == hipSuccess) e = hipMalloc(&p->d_post64, sizeof(double2) * (M + 1));
-        if (e == hipSuccess) e = hipMemcpy(p->d_window64, win.data(), sizeof(double) * nperseg, hipMemcpyHostToDevice);
-        if (e == hipSuccess) e = hipMemcpy(p->d_tw64, tw.data(), sizeof(double2) * M, hipMemcpyHostToDevice);
-        if (e == hipSuccess) e = hipMemcpy(p->d_post64, post.data(), sizeof(double2) * (M + 1), hipMemcpyHostToDevice);
+        (rc = p->d_window64.upload(win.data(), nperseg, "stft plan upload")) ||
+            (rc = p->d_tw64.upload(tw.data(), M, "stft plan upload")) ||
+            (rc = p->d_post64.upload(post.data(), M + 1, "stft plan upload"));
     }
-    if (e != hipSuccess) {
-        msd_stft_plan_destroy(p);
-        return hip_fail(e, "stft plan upload");
-    }
-    *out = p;
+    if (rc) return rc;
+    *out = p.release();
     return MSD_OK;
 }
 
@@ -447,16 +454,12 @@ int stft_psd_host(msd_stft_plan *p, const void *x, int dtype, int64_t n, void *o
     DeviceGuard g(ctx->device);
     const int64_t K = p->M + 1;
     const int64_t ld = (T + 31) / 32 * 32;
-    const size_t xin = ((size_t)n * es + 255) / 256 * 256;
-    void *dx, *dmeta, *dout;
+    const void *dx;
+    const int64_t *doff;
+    void *dout;
     int rc;
-    if ((rc = ctx_scratch(ctx, 0, xin, &dx))) return rc;
-    if ((rc = ctx_scratch(ctx, 1, 64, &dmeta))) return rc;
-    if ((rc = ctx_scratch(ctx, 2, out_es * K * ld, &dout))) return rc;
-    int64_t meta[2] = {0, n};
-    MSD_HIP(hipMemcpyAsync(dx, x, (size_t)n * es, hipMemcpyHostToDevice, ctx->stream));
-    MSD_HIP(hipMemcpyAsync(dmeta, meta, sizeof(meta), hipMemcpyHostToDevice, ctx->stream));
-    const int64_t *doff = static_cast<const int64_t *>(dmeta);
+    if ((rc = stage_one_file(ctx, x, (size_t)n * es, n, &dx, &doff))) return rc;
+    if ((rc = ctx_scratch(ctx, SCRATCH_OUTPUT, out_es * K * ld, &dout))) return rc;
     rc = launch_stft(p, dx, dtype, doff, doff + 1, 1, T, dout, ld);
     if (rc) return rc;
     MSD_HIP(hipMemcpy2DAsync(out, out_es * T, dout, out_es * ld, out_es * T, K, hipMemcpyDeviceToHost, ctx->stream));
@@ -482,20 +485,7 @@ int msd_stft_plan_create_ex(msd_ctx *ctx, int32_t nperseg, int32_t nfft, int32_t
     return stft_plan_make(ctx, nperseg, nfft, hop, nullptr, window, scale, precision, out);
 }
 
-void msd_stft_plan_destroy(msd_stft_plan *p) {
-    if (!p) return;
-    DeviceGuard g(p->ctx->device);
-    hipStreamSynchronize(p->ctx->stream);
-    hipFree(p->d_window);
-    hipFree(p->d_tw);
-    hipFree(p->d_post);
-    hipFree(p->d_window64);
-    hipFree(p->d_tw64);
-    hipFree(p->d_post64);
-    if (p->d_sched) hipFree(p->d_sched);
-    if (p->d_ticket) hipFree(p->d_ticket);
-    delete p;
-}
+void msd_stft_plan_destroy(msd_stft_plan *p) { destroy_plan(p); }
 
 int64_t msd_stft_frames(const msd_stft_plan *p, int64_t n) {
     if (!p || n < p->nperseg) return 0;
@@ -561,7 +551,7 @@ int msd_block_plan_create(msd_ctx *ctx, int64_t block_size, int32_t nfft, const 
     if (!clampband(band_lo, band_hi) || !clampband(noise_lo, noise_hi))
         return fail(MSD_ERR_INVALID, "block plan: band bins outside [0, n_fft/2]");
     DeviceGuard g(ctx->device);
-    auto *p = new msd_block_plan();
+    auto p = std::make_unique<msd_block_plan>();
     p->ctx = ctx;
     p->block_size = block_size;
     p->nfft = nfft;
@@ -599,42 +589,23 @@ int msd_block_plan_create(msd_ctx *ctx, int64_t block_size, int32_t nfft, const 
             bconst.push_back(std::sin(a));
         }
     }
-    hipError_t e = hipMalloc(&p->d_window, sizeof(double) * L);
-    if (e == hipSuccess) e = hipMalloc(&p->d_bconst, sizeof(double) * (bconst.size() + 1));
-    if (e == hipSuccess && !bconst.empty())
-        e = hipMemcpy(p->d_bconst, bconst.data(), sizeof(double) * bconst.size(), hipMemcpyHostToDevice);
-    if (e == hipSuccess) e = hipMalloc(&p->d_tw, sizeof(double2) * nfft);
-    if (e == hipSuccess) e = hipMalloc(&p->d_bins, sizeof(int) * (bins.size() + 1));
-    if (e == hipSuccess) e = hipMemcpy(p->d_window, window, sizeof(double) * L, hipMemcpyHostToDevice);
-    if (e == hipSuccess) e = hipMemcpy(p->d_tw, tw.data(), sizeof(double2) * nfft, hipMemcpyHostToDevice);
-    if (e == hipSuccess && !bins.empty())
-        e = hipMemcpy(p->d_bins, bins.data(), sizeof(int) * bins.size(), hipMemcpyHostToDevice);
-    if (e != hipSuccess) {
-        msd_block_plan_destroy(p);
-        return hip_fail(e, "block plan upload");
-    }
-    if (block_i8_shape(L, p->nbins) && block_i8_window(window, L)) {  // int16 blocks on the matrix cores (block_i8.hip)
-        if (int rc = block_i8_build(p, window, bins.data(), p->nbins)) {
-            msd_block_plan_destroy(p);
-            return rc;
-        }
-    }
-    *out = p;
+    // d_bconst and d_bins hold one element more than is uploaded
+    bconst.push_back(0.0);
+    bins.push_back(0);
+    int rc;
+    (rc = p->d_window.upload(window, L, "block plan upload")) ||
+        (rc = p->d_bconst.upload(bconst.data(), bconst.size(), "block plan upload")) ||
+        (rc = p->d_tw.upload(tw.data(), nfft, "block plan upload")) ||
+        (rc = p->d_bins.upload(bins.data(), bins.size(), "block plan upload"));
+    // int16 blocks on the matrix cores (block_i8.hip)
+    if (!rc && block_i8_shape(L, p->nbins) && block_i8_window(window, L))
+        rc = block_i8_build(p.get(), window, bins.data(), p->nbins);
+    if (rc) return rc;
+    *out = p.release();
     return MSD_OK;
 }
 
-void msd_block_plan_destroy(msd_block_plan *p) {
-    if (!p) return;
-    DeviceGuard g(p->ctx->device);
-    hipStreamSynchronize(p->ctx->stream);
-    hipFree(p->d_window);
-    hipFree(p->d_tw);
-    hipFree(p->d_bins);
-    hipFree(p->d_bconst);
-    hipFree(p->d_energy);
-    hipFree(p->d_i8);
-    delete p;
-}
+void msd_block_plan_destroy(msd_block_plan *p) { destroy_plan(p); }
 
 int msd_block_delta_dev(msd_block_plan *p, const void *x, int dtype, const int64_t *off, const int64_t *len,
                         int64_t nfiles, int64_t max_blocks, double *band_db, double *noise_db, double *delta,
@@ -655,16 +626,13 @@ int msd_block_delta(msd_block_plan *p, const void *x, int dtype, int64_t n, doub
     if (nb == 0) return MSD_OK;
     msd_ctx *ctx = p->ctx;
     DeviceGuard g(ctx->device);
-    void *dx, *dmeta, *dout;
+    const void *dx;
+    const int64_t *doff;
+    void *dout;
     int rc;
-    if ((rc = ctx_scratch(ctx, 0, ((size_t)n * es + 255) / 256 * 256, &dx))) return rc;
-    if ((rc = ctx_scratch(ctx, 1, 64, &dmeta))) return rc;
-    if ((rc = ctx_scratch(ctx, 2, sizeof(double) * 3 * nb, &dout))) return rc;
-    int64_t meta[2] = {0, n};
-    MSD_HIP(hipMemcpyAsync(dx, x, (size_t)n * es, hipMemcpyHostToDevice, ctx->stream));
-    MSD_HIP(hipMemcpyAsync(dmeta, meta, sizeof(meta), hipMemcpyHostToDevice, ctx->stream));
+    if ((rc = stage_one_file(ctx, x, (size_t)n * es, n, &dx, &doff))) return rc;
+    if ((rc = ctx_scratch(ctx, SCRATCH_OUTPUT, sizeof(double) * 3 * nb, &dout))) return rc;
     double *d = static_cast<double *>(dout);
-    const int64_t *doff = static_cast<const int64_t *>(dmeta);
     rc = launch_block_delta(p, dx, dtype, doff, doff + 1, 1, nb, d, d + nb, d + 2 * nb, nb);
     if (rc) return rc;
     if (band_db) MSD_HIP(hipMemcpyAsync(band_db, d, sizeof(double) * nb, hipMemcpyDeviceToHost, ctx->stream));
@@ -703,7 +671,7 @@ int msd_detect(msd_ctx *ctx, const double *delta, int64_t nb, const msd_det_cfg 
     // scratch layout: delta[ld] | thr[ld] | nb | count | margin | status | dets[dcap]
     const size_t bytes = sizeof(double) * 2 * ld + 32 + sizeof(msd_det) * dcap;
     void *s;
-    if ((rc = ctx_scratch(ctx, 3, bytes, &s))) return rc;
+    if ((rc = ctx_scratch(ctx, SCRATCH_DETECTIONS, bytes, &s))) return rc;
     char *base = static_cast<char *>(s);
     double *dd = reinterpret_cast<double *>(base);
     double *dthr = dd + ld;

@@ -476,15 +476,8 @@ __global__ __launch_bounds__(256) void block_long_kernel(
 }
 
 int ensure_energy(msd_block_plan *p, int64_t blocks) {
-    if ((size_t)blocks + 1 > p->energy_cap) {  // grown once per plan (the stream is drained first);
-        MSD_HIP(hipStreamSynchronize(p->ctx->stream));  // + 1: block_i8_kernel's spare slot
-        MSD_HIP(hipFree(p->d_energy));
-        p->d_energy = nullptr;
-        p->energy_cap = 0;
-        MSD_HIP(hipMalloc(&p->d_energy, sizeof(double2) * ((size_t)blocks + 1)));
-        p->energy_cap = (size_t)blocks + 1;
-    }
-    return MSD_OK;
+    // grown once per plan (the stream is drained first); + 1: block_i8_kernel's spare slot
+    return p->d_energy.grow((size_t)blocks + 1, p->ctx->stream, "block plan: energies");
 }
 
 // workgroups of block_long_kernel: a few per CU, each walking whole blocks
@@ -500,11 +493,11 @@ int launch_bdl(msd_block_plan *p, const void *x, const int64_t *off, const int64
     const size_t lds = sizeof(double) * (2 * 2 * 4 * BDL_SW + (size_t)(p->nbins > 0 ? p->nbins : 1));
     hipLaunchKernelGGL((block_long_kernel<T>), dim3((unsigned)bdl_grid(blocks, p->ctx->num_cu)), dim3(256), lds,
                        p->ctx->stream, static_cast<const T *>(x), off, len, nfiles, max_blocks, p->block_size, p->L,
-                       p->nfft, p->spl, p->d_window, p->d_bconst, p->d_tw, p->d_bins, nband, nnoise,
-                       reinterpret_cast<double *>(p->d_energy));
+                       p->nfft, p->spl, p->d_window.get(), p->d_bconst.get(), p->d_tw.get(), p->d_bins.get(), nband, nnoise,
+                       reinterpret_cast<double *>(p->d_energy.get()));
     MSD_HIP(hipGetLastError());
     hipLaunchKernelGGL(block_db_kernel, dim3((unsigned)((blocks + 255) / 256)), dim3(256), 0, p->ctx->stream,
-                       p->d_energy, len, nfiles, max_blocks, p->block_size, band_db, noise_db, delta, ld);
+                       p->d_energy.get(), len, nfiles, max_blocks, p->block_size, band_db, noise_db, delta, ld);
     MSD_HIP(hipGetLastError());
     return MSD_OK;
 }
@@ -521,19 +514,19 @@ int launch_bd2(msd_block_plan *p, const void *x, const int64_t *off, const int64
     const size_t lds = sizeof(double) * (16 * bd2_pitch(SPL) + BD2_GROUPS * (size_t)(p->nbins > 0 ? p->nbins : 1));
     bool done = false;
     if constexpr (std::is_same_v<T, int16_t>) {
-        if (p->d_i8 && !p->ctx->block_goertzel) {  // the exact integer DFT on the matrix cores
+        if (p->d_i8.get() && !p->ctx->block_goertzel) {  // the exact integer DFT on the matrix cores
             if (int rc = launch_block_i8(p, static_cast<const int16_t *>(x), off, len, nfiles, max_blocks)) return rc;
             done = true;
         }
     }
     if (!done)
     hipLaunchKernelGGL((block_delta2_kernel<T, SPL>), dim3((unsigned)grid), dim3(256), lds, p->ctx->stream,
-                       static_cast<const T *>(x), off, len, nfiles, max_blocks, p->block_size, p->L, p->d_window,
-                       p->d_bconst, p->band_hi - p->band_lo + 1 > 0 ? p->band_hi - p->band_lo + 1 : 0,
-                       p->noise_hi - p->noise_lo + 1 > 0 ? p->noise_hi - p->noise_lo + 1 : 0, p->d_energy);
+                       static_cast<const T *>(x), off, len, nfiles, max_blocks, p->block_size, p->L, p->d_window.get(),
+                       p->d_bconst.get(), p->band_hi - p->band_lo + 1 > 0 ? p->band_hi - p->band_lo + 1 : 0,
+                       p->noise_hi - p->noise_lo + 1 > 0 ? p->noise_hi - p->noise_lo + 1 : 0, p->d_energy.get());
     MSD_HIP(hipGetLastError());
     hipLaunchKernelGGL(block_db_kernel, dim3((unsigned)((blocks + 255) / 256)), dim3(256), 0, p->ctx->stream,
-                       p->d_energy, len, nfiles, max_blocks, p->block_size, band_db, noise_db, delta, ld);
+                       p->d_energy.get(), len, nfiles, max_blocks, p->block_size, band_db, noise_db, delta, ld);
     MSD_HIP(hipGetLastError());
     return MSD_OK;
 }
@@ -562,7 +555,7 @@ int launch_bd(msd_block_plan *p, const void *x, const int64_t *off, const int64_
         return rc;
     hipLaunchKernelGGL((block_delta_kernel<T, SPL>), dim3((unsigned)grid), dim3(BD_WAVES * 64), lds, p->ctx->stream,
                        static_cast<const T *>(x), off, len, nfiles, max_blocks, p->block_size, p->L, p->nfft,
-                       p->d_window, p->d_tw, p->d_bins, p->band_hi - p->band_lo + 1 > 0 ? p->band_hi - p->band_lo + 1 : 0,
+                       p->d_window.get(), p->d_tw.get(), p->d_bins.get(), p->band_hi - p->band_lo + 1 > 0 ? p->band_hi - p->band_lo + 1 : 0,
                        p->noise_hi - p->noise_lo + 1 > 0 ? p->noise_hi - p->noise_lo + 1 : 0, band_db, noise_db,
                        delta, ld);
     MSD_HIP(hipGetLastError());

@@ -232,10 +232,9 @@ int block_i8_build(msd_block_plan *p, const double *window, const int *bins, int
                 }
             }
     const size_t nb_frag = frag.size(), nb_init = sizeof(int) * init.size();
-    hipError_t e = hipMalloc(&p->d_i8, nb_frag + nb_init);
-    if (e == hipSuccess) e = hipMemcpy(p->d_i8, frag.data(), nb_frag, hipMemcpyHostToDevice);
-    if (e == hipSuccess)
-        e = hipMemcpy(static_cast<char *>(p->d_i8) + nb_frag, init.data(), nb_init, hipMemcpyHostToDevice);
+    if (int rc = p->d_i8.alloc(nb_frag + nb_init, "block plan: int8 tables")) return rc;
+    hipError_t e = hipMemcpy(p->d_i8.get(), frag.data(), nb_frag, hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = hipMemcpy(p->d_i8.get() + nb_frag, init.data(), nb_init, hipMemcpyHostToDevice);
     if (e != hipSuccess) return hip_fail(e, "block plan: int8 tables");
     return MSD_OK;
 }
@@ -246,9 +245,8 @@ int launch_block_i8(msd_block_plan *p, const int16_t *x, const int64_t *off, con
     const int nband = p->band_hi - p->band_lo + 1 > 0 ? p->band_hi - p->band_lo + 1 : 0;
     const int nnoise = p->noise_hi - p->noise_lo + 1 > 0 ? p->noise_hi - p->noise_lo + 1 : 0;
     const int KS = p->L / 64;
-    const v4i *frag = static_cast<const v4i *>(p->d_i8);
-    const int *init = reinterpret_cast<const int *>(static_cast<const char *>(p->d_i8) +
-                                                    sizeof(v4i) * (size_t)BI_ND * KS * 64);
+    const v4i *frag = reinterpret_cast<const v4i *>(p->d_i8.get());
+    const int *init = reinterpret_cast<const int *>(p->d_i8.get() + sizeof(v4i) * (size_t)BI_ND * KS * 64);
     // persistent: one 8-wave workgroup per CU (the B fragments fill 28-112 KB of LDS), every wave
     // takes every nwaves-th tile, so the chip sweeps the blocks in order
     const int64_t ntiles = (blocks + BI_ROWS - 1) / BI_ROWS;
@@ -258,15 +256,15 @@ int launch_block_i8(msd_block_plan *p, const int16_t *x, const int64_t *off, con
     switch (KS) {
         case 4:
             hipLaunchKernelGGL(block_band_i8_kernel<4>, dim3((unsigned)grid), dim3(64 * BI_WAVES), 0, st, x, off, len, nfiles, max_blocks,
-                               p->block_size, frag, init, nband, nnoise, p->d_energy);
+                               p->block_size, frag, init, nband, nnoise, p->d_energy.get());
             break;
         case 8:
             hipLaunchKernelGGL(block_band_i8_kernel<8>, dim3((unsigned)grid), dim3(64 * BI_WAVES), 0, st, x, off, len, nfiles, max_blocks,
-                               p->block_size, frag, init, nband, nnoise, p->d_energy);
+                               p->block_size, frag, init, nband, nnoise, p->d_energy.get());
             break;
         case 16:
             hipLaunchKernelGGL(block_band_i8_kernel<16>, dim3((unsigned)grid), dim3(64 * BI_WAVES), 0, st, x, off, len, nfiles,
-                               max_blocks, p->block_size, frag, init, nband, nnoise, p->d_energy);
+                               max_blocks, p->block_size, frag, init, nband, nnoise, p->d_energy.get());
             break;
         default: return fail(MSD_ERR_UNSUPPORTED, "block_i8: L");
     }

@@ -383,7 +383,7 @@ int msd_cstft_plan_create_ex(msd_ctx *ctx, int32_t nperseg, int32_t nfft, int32_
     if (hop <= 0 || hop > nperseg) return fail(MSD_ERR_INVALID, "cstft: need 0 < hop <= nperseg");
     if (!(scale > 0)) return fail(MSD_ERR_INVALID, "cstft: scale must be > 0");
     DeviceGuard g(ctx->device);
-    auto *p = new msd_cstft_plan();
+    auto p = std::make_unique<msd_cstft_plan>();
     p->ctx = ctx;
     p->nperseg = nperseg;
     p->nfft = nfft;
@@ -396,28 +396,15 @@ int msd_cstft_plan_create_ex(msd_ctx *ctx, int32_t nperseg, int32_t nfft, int32_
         const double a = -2.0 * M_PI * (double)m / (double)nfft;
         tw[m] = make_float2((float)std::cos(a), (float)std::sin(a));
     }
-    hipError_t e = hipMalloc(&p->d_win, sizeof(float) * nperseg);
-    if (e == hipSuccess) e = hipMalloc(&p->d_tw, sizeof(float2) * nfft);
-    if (e == hipSuccess) e = hipMemcpy(p->d_win, w.data(), sizeof(float) * nperseg, hipMemcpyHostToDevice);
-    if (e == hipSuccess) e = hipMemcpy(p->d_tw, tw.data(), sizeof(float2) * nfft, hipMemcpyHostToDevice);
-    if (e != hipSuccess) {
-        msd_cstft_plan_destroy(p);
-        return hip_fail(e, "msd_cstft_plan_create");
-    }
-    *out = p;
+    int rc;
+    (rc = p->d_win.upload(w.data(), nperseg, "msd_cstft_plan_create")) ||
+        (rc = p->d_tw.upload(tw.data(), nfft, "msd_cstft_plan_create"));
+    if (rc) return rc;
+    *out = p.release();
     return MSD_OK;
 }
 
-void msd_cstft_plan_destroy(msd_cstft_plan *p) {
-    if (!p) return;
-    DeviceGuard g(p->ctx->device);
-    (void)hipStreamSynchronize(p->ctx->stream);
-    if (p->d_win) (void)hipFree(p->d_win);
-    if (p->d_tw) (void)hipFree(p->d_tw);
-    if (p->d_sched) (void)hipFree(p->d_sched);
-    if (p->d_ticket) (void)hipFree(p->d_ticket);
-    delete p;
-}
+void msd_cstft_plan_destroy(msd_cstft_plan *p) { destroy_plan(p); }
 
 int msd_cstft_set_detrend(msd_cstft_plan *p, int detrend) {
     if (!p || (detrend != 0 && detrend != 1)) return fail(MSD_ERR_INVALID, "msd_cstft_set_detrend: bad args");
@@ -472,7 +459,7 @@ int msd_cstft_psd_fsums_dev(msd_cstft_plan *p, const void *x, int dtype, const i
         wgs = (total + per - 1) / per;
         KernelTimer timer(p->ctx, K_CSTFT);  // the FFT kernel alone: the roofline's
         hipLaunchKernelGGL(kern, dim3((unsigned)wgs), dim3(CS_T), 0, p->ctx->stream, xp, off, len, nstreams,
-                           max_frames, total, per, p->hop, p->detrend, p->d_win, p->d_tw, out, etot,
+                           max_frames, total, per, p->hop, p->detrend, p->d_win.get(), p->d_tw.get(), out, etot,
                            msd_cstft_energy_stride(nstreams, max_frames), fsum, nullptr, (int64_t)0, nullptr);
         return MSD_OK;
     };
@@ -480,40 +467,17 @@ int msd_cstft_psd_fsums_dev(msd_cstft_plan *p, const void *x, int dtype, const i
     // change, and the ticket zeroed on the stream before every launch
     auto launch_dyn = [&](auto kern, const auto *xp) -> int {
         const int64_t wgs = grid(kern);
-        if (p->sched_total != total || p->sched_wgs != wgs) {
-            std::vector<int64_t> st(1, 0);
-            // guided: each chunk 1 / (div * wgs) of what is left, at least cmin frames (bench C5 on
-            // one box, profiles/r5_c5_sched_overlap.txt: div 1 13.06 ms, 2 10.19, 4 9.73-9.81, 8 9.81,
-            // 16 9.88; fixed 16 / 32 / 64 / 128-frame chunks 9.95 / 9.91 / 9.94 / 10.02 -- the
-            // workgroups working on nearby frames, not only the balance, pays)
-            constexpr int64_t cmin = 16, div = 4;
-            for (int64_t pos = 0; pos < total;) {
-                int64_t sz = (total - pos) / (div * wgs);
-                sz = (std::max<int64_t>(sz, cmin) + 3) / 4 * 4;
-                pos = std::min(total, pos + sz);
-                st.push_back(pos);
-            }
-            DeviceGuard dg(p->ctx->device);
-            MSD_HIP(hipStreamSynchronize(p->ctx->stream));
-            if ((int64_t)st.size() > p->sched_cap) {
-                if (p->d_sched) MSD_HIP(hipFree(p->d_sched));
-                p->d_sched = nullptr;
-                p->sched_cap = 0;
-                MSD_HIP(hipMalloc(&p->d_sched, sizeof(int64_t) * st.size()));
-                p->sched_cap = (int64_t)st.size();
-            }
-            if (!p->d_ticket) MSD_HIP(hipMalloc(&p->d_ticket, sizeof(unsigned long long)));
-            MSD_HIP(hipMemcpy(p->d_sched, st.data(), sizeof(int64_t) * st.size(), hipMemcpyHostToDevice));
-            p->sched_total = total;
-            p->sched_wgs = wgs;
-            p->sched_n = (int64_t)st.size() - 1;
-        }
-        MSD_HIP(hipMemsetAsync(p->d_ticket, 0, sizeof(unsigned long long), p->ctx->stream));
+        // guided: each chunk 1 / (div * wgs) of what is left, at least cmin frames, in whole groups
+        // of 4; div = 4, cmin = 16 (bench C5 on one box, profiles/r5_c5_sched_overlap.txt: div 1
+        // 13.06 ms, 2 10.19, 4 9.73-9.81, 8 9.81, 16 9.88; fixed 16 / 32 / 64 / 128-frame chunks
+        // 9.95 / 9.91 / 9.94 / 10.02 -- the workgroups working on nearby frames, not only the
+        // balance, pays)
+        if (int rc = guided_sched_prepare(p->sched, p->ctx->stream, total, wgs, 4, 16, 4, false)) return rc;
         KernelTimer timer(p->ctx, K_CSTFT);
         hipLaunchKernelGGL(kern, dim3((unsigned)wgs), dim3(CS_T), 0, p->ctx->stream, xp, off, len, nstreams,
-                           max_frames, total, (int64_t)0, p->hop, p->detrend, p->d_win, p->d_tw, out, etot,
-                           msd_cstft_energy_stride(nstreams, max_frames), fsum, p->d_sched, p->sched_n,
-                           p->d_ticket);
+                           max_frames, total, (int64_t)0, p->hop, p->detrend, p->d_win.get(), p->d_tw.get(), out, etot,
+                           msd_cstft_energy_stride(nstreams, max_frames), fsum, p->sched.bounds.get(), p->sched.n,
+                           p->sched.ticket.get());
         return MSD_OK;
     };
     const int sh = p->hop % 256 == 0 ? p->hop / 256 : 0;
@@ -554,15 +518,12 @@ int msd_cstft_psd(msd_cstft_plan *p, const void *x, int dtype, int64_t n, float 
     if (T == 0) return MSD_OK;
     msd_ctx *ctx = p->ctx;
     DeviceGuard g(ctx->device);
-    void *dx, *dmeta, *dout;
+    const void *dx;
+    const int64_t *doff;
+    void *dout;
     int rc;
-    if ((rc = ctx_scratch(ctx, 0, ((size_t)n * es + 255) / 256 * 256, &dx))) return rc;
-    if ((rc = ctx_scratch(ctx, 1, 64, &dmeta))) return rc;
-    if ((rc = ctx_scratch(ctx, 2, sizeof(float) * (size_t)p->nfft * (size_t)T, &dout))) return rc;
-    int64_t meta[2] = {0, n};
-    MSD_HIP(hipMemcpyAsync(dx, x, (size_t)n * es, hipMemcpyHostToDevice, ctx->stream));
-    MSD_HIP(hipMemcpyAsync(dmeta, meta, sizeof(meta), hipMemcpyHostToDevice, ctx->stream));
-    const int64_t *doff = static_cast<const int64_t *>(dmeta);
+    if ((rc = stage_one_file(ctx, x, (size_t)n * es, n, &dx, &doff))) return rc;
+    if ((rc = ctx_scratch(ctx, SCRATCH_OUTPUT, sizeof(float) * (size_t)p->nfft * (size_t)T, &dout))) return rc;
     rc = msd_cstft_psd_dev(p, dx, dtype, doff, doff + 1, 1, T, static_cast<float *>(dout));
     if (rc) return rc;
     MSD_HIP(hipMemcpyAsync(out, dout, sizeof(float) * (size_t)p->nfft * (size_t)T, hipMemcpyDeviceToHost, ctx->stream));

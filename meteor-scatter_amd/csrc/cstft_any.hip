@@ -411,7 +411,7 @@ int launch_l(msd_cstft_plan *p, const T *x, const int64_t *off, const int64_t *l
     wgs = (ngroups + per - 1) / per;
     KernelTimer timer(p->ctx, K_CSTFT);
     hipLaunchKernelGGL(kern, dim3((unsigned)wgs), dim3(S::TPB), S::LDS_BYTES, p->ctx->stream, x, off, len, max_frames,
-                       total, ngroups, per, p->nperseg, p->hop, p->detrend, p->d_win, p->d_tw, out, etot,
+                       total, ngroups, per, p->nperseg, p->hop, p->detrend, p->d_win.get(), p->d_tw.get(), out, etot,
                        msd_cstft_energy_stride(nstreams, max_frames));
     return MSD_OK;
 }

@@ -16,6 +16,8 @@
 //   host_check i8 SEED ITERS       i8_digits.h: balanced_digits<6> / <7> over ITERS random T and the
 //                                  edges, zero_sum_round on detrended Hann coefficients, the two band
 //                                  kernels' coefficient functions, frag_sample
+//   host_check sched TOTAL WGS DIV CMIN MULTIPLE MERGE
+//                                  guided_sched.h: "ok" and the chunk bounds of guided_chunks
 #include <fcntl.h>
 #include <unistd.h>
 
@@ -28,6 +30,7 @@
 #include <string>
 #include <vector>
 
+#include "guided_sched.h"
 #include "i8_digits.h"
 #include "np_program.h"
 #include "refine_plan.h"
@@ -553,6 +556,16 @@ int cmd_i8(uint64_t seed, int64_t iters) {
     return 0;
 }
 
+int cmd_sched(char **argv) {
+    std::vector<int64_t> bounds;
+    msd::guided_chunks(std::atoll(argv[0]), std::atoll(argv[1]), std::atoll(argv[2]), std::atoll(argv[3]),
+                       std::atoll(argv[4]), std::atoi(argv[5]) != 0, bounds);
+    std::printf("ok");
+    for (int64_t b : bounds) std::printf(" %" PRId64, b);
+    std::printf("\n");
+    return 0;
+}
+
 }  // namespace
 
 int main(int argc, char **argv) {
@@ -561,7 +574,8 @@ int main(int argc, char **argv) {
     if (argc >= 9 && !std::strcmp(argv[1], "refine")) return cmd_refine(argc - 2, argv + 2);
     if (argc >= 4 && !std::strcmp(argv[1], "fuzz")) return cmd_fuzz(std::strtoull(argv[2], nullptr, 10), std::atoll(argv[3]));
     if (argc >= 4 && !std::strcmp(argv[1], "i8")) return cmd_i8(std::strtoull(argv[2], nullptr, 10), std::atoll(argv[3]));
+    if (argc >= 8 && !std::strcmp(argv[1], "sched")) return cmd_sched(argv + 2);
     std::fprintf(stderr, "usage: host_check wav FILE | program N | refine N HOP BLO BHI NLO NHI NSAMP [A B]... | "
-                         "fuzz SEED ITERS | i8 SEED ITERS\n");
+                         "fuzz SEED ITERS | i8 SEED ITERS | sched TOTAL WGS DIV CMIN MULTIPLE MERGE\n");
     return 2;
 }

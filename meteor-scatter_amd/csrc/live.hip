@@ -524,7 +524,7 @@ int launch_welch_t(msd_welch_plan *p, const void *x, const int64_t *off, const i
     if (grid > 0x7fffffffLL) return fail(MSD_ERR_UNSUPPORTED, "welch: grid too large");
     KernelTimer timer(p->ctx, K_WELCH);
     hipLaunchKernelGGL(welch_bands_kernel<T>, dim3((unsigned)grid), dim3(64 * nw), lds, p->ctx->stream,
-                       static_cast<const T *>(x), off, len, A, p->d_window, p->d_bins, band_db, psd);
+                       static_cast<const T *>(x), off, len, A, p->d_window.get(), p->d_bins.get(), band_db, psd);
     MSD_HIP(hipGetLastError());
     return MSD_OK;
 }
@@ -532,7 +532,7 @@ int launch_welch_t(msd_welch_plan *p, const void *x, const int64_t *off, const i
 int launch_welch(msd_welch_plan *p, const void *x, int dtype, const int64_t *off, const int64_t *len, int64_t nfiles,
                  int64_t max_blocks, double *band_db, int64_t ld, double *psd) {
     if (nfiles == 0 || max_blocks == 0) return MSD_OK;
-    if (dtype == MSD_I16 && p->d_i8 && !p->ctx->welch_goertzel)  // the exact integer DFT (welch_i8.hip)
+    if (dtype == MSD_I16 && p->d_i8.get() && !p->ctx->welch_goertzel)  // the exact integer DFT (welch_i8.hip)
         return launch_welch_i8(p, static_cast<const int16_t *>(x), off, len, nfiles, max_blocks, band_db, ld, psd);
     switch (dtype) {
         case MSD_U8: return launch_welch_t<uint8_t>(p, x, off, len, nfiles, max_blocks, band_db, ld, psd);
@@ -566,7 +566,7 @@ int launch_live(msd_ctx *ctx, const double *band_db, const int64_t *nblocks, int
     const size_t b_state = sizeof(LiveScan) * (size_t)nseg, b_cnt = sizeof(int64_t) * (size_t)nseg,
                  b_act = sizeof(int32_t) * (size_t)nseg;
     void *sp = nullptr;
-    if (int rc = ctx_scratch(ctx, 6, 2 * b_state + b_cnt + b_act + 64, &sp)) return rc;
+    if (int rc = ctx_scratch(ctx, SCRATCH_LIVE_SEGMENTS, 2 * b_state + b_cnt + b_act + 64, &sp)) return rc;
     char *base = static_cast<char *>(sp);
     LiveSegState S;
     S.in = reinterpret_cast<LiveScan *>(base);
@@ -794,23 +794,24 @@ struct msd_live_session {
     msd_welch_plan *plan = nullptr;  // null: rows only
     int dtype = 0;
     int64_t F = 0, P = 0, H = 0, stride = 0;  // stride: samples per stream of the staging buffer
-    msd_live_stream_state *d_state = nullptr;
-    double *d_hist = nullptr;   // [F][H + P]
-    double *d_thr = nullptr;    // [F][P]      thresholds / over / band rows of a push whose caller
-    double *d_over = nullptr;   // [F][P]      passes no buffer of its own
-    double *d_band = nullptr;   // [F][3][P]
-    void *d_stage = nullptr;    // [F][stride] samples
-    void *d_rem = nullptr;      // [F][block_size] samples
-    int64_t *d_meta = nullptr;  // [4][F] gather's Welch offsets / lengths, block counts, remainders
-    int64_t *d_aux = nullptr;   // [4][F] the host forms' nblocks / off / len, counts, new blocks
-    int32_t *d_status = nullptr;
+    DevBuf<msd_live_stream_state> d_state;
+    DevBuf<double> d_hist;   // [F][H + P]
+    DevBuf<double> d_thr;    // [F][P]      thresholds / over / band rows of a push whose caller
+    DevBuf<double> d_over;   // [F][P]      passes no buffer of its own
+    DevBuf<double> d_band;   // [F][3][P]
+    DevBuf<char> d_stage;    // [F][stride] samples
+    DevBuf<char> d_rem;      // [F][block_size] samples
+    DevBuf<int64_t> d_meta;  // [4][F] gather's Welch offsets / lengths, block counts, remainders
+    DevBuf<int64_t> d_aux;   // [4][F] the host forms' nblocks / off / len, counts, new blocks
+    DevBuf<int32_t> d_status;
+    ~msd_live_session() { msd_welch_plan_destroy(plan); }
 };
 
 namespace {
 
 int ls_reset(msd_live_session *s, int64_t first, int64_t n) {
     hipLaunchKernelGGL(live_session_reset_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s->ctx->stream,
-                       s->d_state, first, n);
+                       s->d_state.get(), first, n);
     MSD_HIP(hipGetLastError());
     return MSD_OK;
 }
@@ -830,13 +831,13 @@ int ls_detect(msd_live_session *s, const double *band_db, const int64_t *nblocks
     KernelTimer timer(s->ctx, K_LIVE);
     if (max_blocks > 0) {
         const dim3 grid((unsigned)((max_blocks + WL_THREADS - 1) / WL_THREADS), (unsigned)s->F);
-        hipLaunchKernelGGL(live_session_over_kernel, grid, dim3(WL_THREADS), 0, st, band_db, ld, nblocks, A, s->d_state,
-                           s->d_hist, over, ld_over);
-        hipLaunchKernelGGL(live_session_history_kernel, grid, dim3(WL_THREADS), 0, st, nblocks, A, s->d_state,
-                           s->d_hist, thr, ld_thr);
+        hipLaunchKernelGGL(live_session_over_kernel, grid, dim3(WL_THREADS), 0, st, band_db, ld, nblocks, A, s->d_state.get(),
+                           s->d_hist.get(), over, ld_over);
+        hipLaunchKernelGGL(live_session_history_kernel, grid, dim3(WL_THREADS), 0, st, nblocks, A, s->d_state.get(),
+                           s->d_hist.get(), thr, ld_thr);
     }
     hipLaunchKernelGGL(live_session_scan_kernel, dim3((unsigned)((s->F + 3) / 4)), dim3(256), 0, st, nblocks, A,
-                       s->d_state, s->d_hist, thr, ld_thr, out, counts, status, new_blocks, new_rem);
+                       s->d_state.get(), s->d_hist.get(), thr, ld_thr, out, counts, status, new_blocks, new_rem);
     MSD_HIP(hipGetLastError());
     return MSD_OK;
 }
@@ -847,12 +848,12 @@ int ls_gather(msd_live_session *s, const void *x, const int64_t *off, const int6
     hipStream_t st = s->ctx->stream;
     const dim3 grid((unsigned)((B + max_len + 255) / 256), (unsigned)s->F);
     KernelTimer timer(s->ctx, K_WELCH);  // the Welch launch's ingest
+    E *stage = reinterpret_cast<E *>(s->d_stage.get()), *rem = reinterpret_cast<E *>(s->d_rem.get());
     hipLaunchKernelGGL(live_session_gather_kernel<E>, grid, dim3(256), 0, st, static_cast<const E *>(x), off, len,
-                       max_len, s->F, B, s->d_state, static_cast<const E *>(s->d_rem), static_cast<E *>(s->d_stage),
-                       s->stride, s->d_meta);
+                       max_len, s->F, B, s->d_state.get(), static_cast<const E *>(rem), stage, s->stride,
+                       s->d_meta.get());
     hipLaunchKernelGGL(live_session_carry_kernel<E>, dim3((unsigned)((B + 255) / 256), (unsigned)s->F), dim3(256), 0,
-                       st, s->F, B, s->d_state, static_cast<const E *>(s->d_stage), s->stride, s->d_meta,
-                       static_cast<E *>(s->d_rem));
+                       st, s->F, B, s->d_state.get(), static_cast<const E *>(stage), s->stride, s->d_meta.get(), rem);
     MSD_HIP(hipGetLastError());
     return MSD_OK;
 }
@@ -887,40 +888,23 @@ int msd_welch_plan_create(msd_ctx *ctx, const msd_welch_cfg *cfg, const double *
         }
     }
     DeviceGuard g(ctx->device);
-    auto *p = new msd_welch_plan();
+    auto p = std::make_unique<msd_welch_plan>();
     p->ctx = ctx;
     p->cfg = c;
     p->step = c.nperseg - c.noverlap;
     p->nseg = (c.block_size - c.nperseg) / p->step + 1;
     p->nslots = nslots;
-    hipError_t e = hipMalloc(&p->d_window, sizeof(double) * c.nperseg);
-    if (e == hipSuccess) e = hipMalloc(&p->d_bins, sizeof(double) * 4 * (nslots > 0 ? nslots : 1));
-    if (e == hipSuccess) e = hipMemcpy(p->d_window, window, sizeof(double) * c.nperseg, hipMemcpyHostToDevice);
-    if (e == hipSuccess && nslots)
-        e = hipMemcpy(p->d_bins, bins.data(), sizeof(double) * bins.size(), hipMemcpyHostToDevice);
-    if (e != hipSuccess) {
-        msd_welch_plan_destroy(p);
-        return hip_fail(e, "msd_welch_plan_create");
-    }
-    if (welch_i8_shape(c, p->nseg, nslots, window)) {  // int16 samples on the matrix cores
-        if (int rc = welch_i8_build(p, window)) {
-            msd_welch_plan_destroy(p);
-            return rc;
-        }
-    }
-    *out = p;
+    if (!nslots) bins.resize(4, 0.0);  // d_bins is never empty
+    int rc;
+    (rc = p->d_window.upload(window, c.nperseg, "msd_welch_plan_create")) ||
+        (rc = p->d_bins.upload(bins.data(), bins.size(), "msd_welch_plan_create"));
+    if (!rc && welch_i8_shape(c, p->nseg, nslots, window)) rc = welch_i8_build(p.get(), window);  // int16 on the matrix cores
+    if (rc) return rc;
+    *out = p.release();
     return MSD_OK;
 }
 
-void msd_welch_plan_destroy(msd_welch_plan *p) {
-    if (!p) return;
-    DeviceGuard g(p->ctx->device);
-    (void)hipStreamSynchronize(p->ctx->stream);
-    if (p->d_window) (void)hipFree(p->d_window);
-    if (p->d_bins) (void)hipFree(p->d_bins);
-    if (p->d_i8) (void)hipFree(p->d_i8);
-    delete p;
-}
+void msd_welch_plan_destroy(msd_welch_plan *p) { destroy_plan(p); }
 
 int msd_welch_bands_dev(msd_welch_plan *p, const void *x, int dtype, const int64_t *off, const int64_t *len,
                         int64_t nfiles, int64_t max_blocks, double *band_db, int64_t ld, double *psd) {
@@ -940,16 +924,13 @@ int msd_welch_bands(msd_welch_plan *p, const void *x, int dtype, int64_t n, doub
     if (nb == 0) return MSD_OK;
     msd_ctx *ctx = p->ctx;
     DeviceGuard g(ctx->device);
-    void *dx, *dmeta, *dout;
+    const void *dx;
+    const int64_t *doff;
+    void *dout;
     int rc;
     const int nbands = p->cfg.nbands;
-    if ((rc = ctx_scratch(ctx, 0, ((size_t)n * es + 255) / 256 * 256, &dx))) return rc;
-    if ((rc = ctx_scratch(ctx, 1, 64, &dmeta))) return rc;
-    if ((rc = ctx_scratch(ctx, 2, sizeof(double) * nbands * nb, &dout))) return rc;
-    int64_t meta[2] = {0, n};
-    MSD_HIP(hipMemcpyAsync(dx, x, (size_t)n * es, hipMemcpyHostToDevice, ctx->stream));
-    MSD_HIP(hipMemcpyAsync(dmeta, meta, sizeof(meta), hipMemcpyHostToDevice, ctx->stream));
-    const int64_t *doff = static_cast<const int64_t *>(dmeta);
+    if ((rc = stage_one_file(ctx, x, (size_t)n * es, n, &dx, &doff))) return rc;
+    if ((rc = ctx_scratch(ctx, SCRATCH_OUTPUT, sizeof(double) * nbands * nb, &dout))) return rc;
     rc = launch_welch(p, dx, dtype, doff, doff + 1, 1, nb, static_cast<double *>(dout), nb, nullptr);
     if (rc) return rc;
     MSD_HIP(hipMemcpyAsync(band_db, dout, sizeof(double) * nbands * nb, hipMemcpyDeviceToHost, ctx->stream));
@@ -967,17 +948,14 @@ int msd_welch_psd(msd_welch_plan *p, const void *x, int dtype, int64_t n, double
     if (nb == 0) return MSD_OK;
     msd_ctx *ctx = p->ctx;
     DeviceGuard g(ctx->device);
-    void *dx, *dmeta, *dout;
+    const void *dx;
+    const int64_t *doff;
+    void *dout;
     int rc;
     const int nbands = p->cfg.nbands;
     const size_t band_bytes = sizeof(double) * nbands * nb, psd_bytes = sizeof(double) * (size_t)p->nslots * nb;
-    if ((rc = ctx_scratch(ctx, 0, ((size_t)n * es + 255) / 256 * 256, &dx))) return rc;
-    if ((rc = ctx_scratch(ctx, 1, 64, &dmeta))) return rc;
-    if ((rc = ctx_scratch(ctx, 2, band_bytes + psd_bytes, &dout))) return rc;
-    int64_t meta[2] = {0, n};
-    MSD_HIP(hipMemcpyAsync(dx, x, (size_t)n * es, hipMemcpyHostToDevice, ctx->stream));
-    MSD_HIP(hipMemcpyAsync(dmeta, meta, sizeof(meta), hipMemcpyHostToDevice, ctx->stream));
-    const int64_t *doff = static_cast<const int64_t *>(dmeta);
+    if ((rc = stage_one_file(ctx, x, (size_t)n * es, n, &dx, &doff))) return rc;
+    if ((rc = ctx_scratch(ctx, SCRATCH_OUTPUT, band_bytes + psd_bytes, &dout))) return rc;
     double *dband = static_cast<double *>(dout);
     double *dpsd = reinterpret_cast<double *>(static_cast<char *>(dout) + band_bytes);
     rc = launch_welch(p, dx, dtype, doff, doff + 1, 1, nb, dband, nb, dpsd);
@@ -1016,7 +994,7 @@ int msd_live_detect(msd_ctx *ctx, const double *band_db, int64_t nb, const msd_l
     // scratch: band_db[3*ld] | over[ld] | thr[ld] | nb | count | status(pad) | meteors[dcap]
     const size_t head = sizeof(double) * 5 * ld + 32;
     void *s;
-    if ((rc = ctx_scratch(ctx, 3, head + sizeof(msd_meteor) * dcap, &s))) return rc;
+    if ((rc = ctx_scratch(ctx, SCRATCH_DETECTIONS, head + sizeof(msd_meteor) * dcap, &s))) return rc;
     char *base = static_cast<char *>(s);
     double *dband = reinterpret_cast<double *>(base);
     double *dover = dband + 3 * ld;
@@ -1072,46 +1050,25 @@ int msd_live_session_create(msd_ctx *ctx, const msd_live_cfg *cfg, const msd_wel
     s->P = max_push_blocks;
     s->H = hist_blocks;
     const size_t F = (size_t)nstreams, P = (size_t)max_push_blocks, H = (size_t)hist_blocks;
-    hipError_t e = hipMalloc(&s->d_state, sizeof(msd_live_stream_state) * F);
-    if (e == hipSuccess) e = hipMalloc(&s->d_hist, sizeof(double) * F * (H + P));
-    if (e == hipSuccess) e = hipMalloc(&s->d_thr, sizeof(double) * F * P);
-    if (e == hipSuccess) e = hipMalloc(&s->d_over, sizeof(double) * F * P);
-    if (e == hipSuccess) e = hipMalloc(&s->d_meta, sizeof(int64_t) * 4 * F);
-    if (e == hipSuccess) e = hipMalloc(&s->d_aux, sizeof(int64_t) * 4 * F);
-    if (e == hipSuccess) e = hipMalloc(&s->d_status, sizeof(int32_t) * F);
-    if (e == hipSuccess && welch) {
+    const char *what = "msd_live_session_create";
+    (rc = s->d_state.alloc(F, what)) || (rc = s->d_hist.alloc(F * (H + P), what)) ||
+        (rc = s->d_thr.alloc(F * P, what)) || (rc = s->d_over.alloc(F * P, what)) ||
+        (rc = s->d_meta.alloc(4 * F, what)) || (rc = s->d_aux.alloc(4 * F, what)) || (rc = s->d_status.alloc(F, what));
+    if (!rc && welch) {
         const size_t es = dtype_size(dtype), B = (size_t)cfg->block_size;
         s->stride = (int64_t)(((P + 1) * B + 63) / 64 * 64);  // every stream's blocks aligned as a file's are
-        e = hipMalloc(&s->d_band, sizeof(double) * F * 3 * P);
-        if (e == hipSuccess) e = hipMalloc(&s->d_stage, es * F * (size_t)s->stride + 256);
-        if (e == hipSuccess) e = hipMalloc(&s->d_rem, es * F * B);
+        (rc = s->d_band.alloc(F * 3 * P, what)) || (rc = s->d_stage.alloc(es * F * (size_t)s->stride + 256, what)) ||
+            (rc = s->d_rem.alloc(es * F * B, what)) || (rc = msd_welch_plan_create(ctx, welch, window, &s->plan));
     }
-    if (e != hipSuccess) {
-        msd_live_session_destroy(s);
-        return hip_fail(e, "msd_live_session_create");
-    }
-    if (welch && (rc = msd_welch_plan_create(ctx, welch, window, &s->plan))) {
-        msd_live_session_destroy(s);
-        return rc;
-    }
-    if ((rc = ls_reset(s, 0, s->F))) {
-        msd_live_session_destroy(s);
+    if (rc || (rc = ls_reset(s, 0, s->F))) {
+        msd_live_session_destroy(s);  // (drains the stream: the reset may be in flight)
         return rc;
     }
     *out = s;
     return MSD_OK;
 }
 
-void msd_live_session_destroy(msd_live_session *s) {
-    if (!s) return;
-    DeviceGuard g(s->ctx->device);
-    (void)hipStreamSynchronize(s->ctx->stream);
-    if (s->plan) msd_welch_plan_destroy(s->plan);
-    for (void *p : {(void *)s->d_state, (void *)s->d_hist, (void *)s->d_thr, (void *)s->d_over, (void *)s->d_band,
-                    s->d_stage, s->d_rem, (void *)s->d_meta, (void *)s->d_aux, (void *)s->d_status})
-        if (p) (void)hipFree(p);
-    delete s;
-}
+void msd_live_session_destroy(msd_live_session *s) { destroy_plan(s); }
 
 int msd_live_session_push_rows_dev(msd_live_session *s, const double *band_db, const int64_t *nblocks,
                                    int64_t max_blocks, int64_t ld, msd_meteor *out, int64_t cap, int64_t *counts,
@@ -1121,8 +1078,8 @@ int msd_live_session_push_rows_dev(msd_live_session *s, const double *band_db, c
     if (max_blocks < 0 || max_blocks > s->P || max_blocks > ld || cap < 0)
         return fail(MSD_ERR_INVALID, "msd_live_session_push_rows_dev: need 0 <= max_blocks <= min(ld, max_push_blocks)");
     DeviceGuard g(s->ctx->device);
-    return ls_detect(s, band_db, nblocks, max_blocks, ld, out, cap, counts, thresholds ? thresholds : s->d_thr,
-                     thresholds ? ld : s->P, over ? over : s->d_over, over ? ld : s->P, status, nullptr, nullptr);
+    return ls_detect(s, band_db, nblocks, max_blocks, ld, out, cap, counts, thresholds ? thresholds : s->d_thr.get(),
+                     thresholds ? ld : s->P, over ? over : s->d_over.get(), over ? ld : s->P, status, nullptr, nullptr);
 }
 
 int msd_live_session_push_samples_dev(msd_live_session *s, const void *x, const int64_t *off, const int64_t *len,
@@ -1147,15 +1104,15 @@ int msd_live_session_push_samples_dev(msd_live_session *s, const void *x, const 
         default: rc = ls_gather<uint64_t>(s, x, off, len, max_len); break;
     }
     if (rc) return rc;
-    double *band = band_db ? band_db : s->d_band;
+    double *band = band_db ? band_db : s->d_band.get();
     const int64_t ld_band = band_db ? ld : s->P;
     const int64_t F = s->F;
-    if ((rc = launch_welch(s->plan, s->d_stage, s->dtype, s->d_meta, s->d_meta + F, F, max_blocks, band, ld_band,
+    if ((rc = launch_welch(s->plan, s->d_stage.get(), s->dtype, s->d_meta.get(), s->d_meta.get() + F, F, max_blocks, band, ld_band,
                            nullptr)))
         return rc;
-    return ls_detect(s, band, s->d_meta + 2 * F, max_blocks, ld_band, out, cap, counts,
-                     thresholds ? thresholds : s->d_thr, thresholds ? ld : s->P, over ? over : s->d_over,
-                     over ? ld : s->P, status, new_blocks, s->d_meta + 3 * F);
+    return ls_detect(s, band, s->d_meta.get() + 2 * F, max_blocks, ld_band, out, cap, counts,
+                     thresholds ? thresholds : s->d_thr.get(), thresholds ? ld : s->P, over ? over : s->d_over.get(),
+                     over ? ld : s->P, status, new_blocks, s->d_meta.get() + 3 * F);
 }
 
 // the host forms' epilogue: stream f's count, status, meteors and the new blocks' values to the host
@@ -1166,9 +1123,9 @@ static int ls_fetch(msd_live_session *s, int64_t f, const msd_meteor *dmet, int6
     const int64_t F = s->F;
     int64_t cnt = 0, nb = 0;
     int32_t stat = 0;
-    MSD_HIP(hipMemcpyAsync(&cnt, s->d_aux + 2 * F + f, sizeof(cnt), hipMemcpyDeviceToHost, st));
-    MSD_HIP(hipMemcpyAsync(&stat, s->d_status + f, sizeof(stat), hipMemcpyDeviceToHost, st));
-    MSD_HIP(hipMemcpyAsync(&nb, s->d_aux + 3 * F + f, sizeof(nb), hipMemcpyDeviceToHost, st));
+    MSD_HIP(hipMemcpyAsync(&cnt, s->d_aux.get() + 2 * F + f, sizeof(cnt), hipMemcpyDeviceToHost, st));
+    MSD_HIP(hipMemcpyAsync(&stat, s->d_status.get() + f, sizeof(stat), hipMemcpyDeviceToHost, st));
+    MSD_HIP(hipMemcpyAsync(&nb, s->d_aux.get() + 3 * F + f, sizeof(nb), hipMemcpyDeviceToHost, st));
     MSD_HIP(hipStreamSynchronize(st));
     *count = cnt;
     if (new_blocks) *new_blocks = nb;
@@ -1179,9 +1136,9 @@ static int ls_fetch(msd_live_session *s, int64_t f, const msd_meteor *dmet, int6
         const size_t bytes = sizeof(double) * (size_t)nb;
         if (band_db)
             for (int j = 0; j < 3; ++j)
-                MSD_HIP(hipMemcpyAsync(band_db + j * ld, s->d_band + (f * 3 + j) * s->P, bytes, hipMemcpyDeviceToHost, st));
-        if (thresholds) MSD_HIP(hipMemcpyAsync(thresholds, s->d_thr + f * s->P, bytes, hipMemcpyDeviceToHost, st));
-        if (over) MSD_HIP(hipMemcpyAsync(over, s->d_over + f * s->P, bytes, hipMemcpyDeviceToHost, st));
+                MSD_HIP(hipMemcpyAsync(band_db + j * ld, s->d_band.get() + (f * 3 + j) * s->P, bytes, hipMemcpyDeviceToHost, st));
+        if (thresholds) MSD_HIP(hipMemcpyAsync(thresholds, s->d_thr.get() + f * s->P, bytes, hipMemcpyDeviceToHost, st));
+        if (over) MSD_HIP(hipMemcpyAsync(over, s->d_over.get() + f * s->P, bytes, hipMemcpyDeviceToHost, st));
     }
     MSD_HIP(hipStreamSynchronize(st));
     if (cnt > cap) return fail(MSD_ERR_CAPACITY, "live session: more meteors than capacity");
@@ -1201,17 +1158,17 @@ int msd_live_session_push_rows(msd_live_session *s, int64_t stream, const double
     const size_t b_rows = sizeof(double) * 3 * (size_t)ld * (size_t)F;
     void *sp;
     int rc;
-    if ((rc = ctx_scratch(ctx, 3, b_rows + sizeof(msd_meteor) * (size_t)dcap * (size_t)F, &sp))) return rc;
+    if ((rc = ctx_scratch(ctx, SCRATCH_DETECTIONS, b_rows + sizeof(msd_meteor) * (size_t)dcap * (size_t)F, &sp))) return rc;
     double *drows = static_cast<double *>(sp);
     msd_meteor *dmet = reinterpret_cast<msd_meteor *>(static_cast<char *>(sp) + b_rows);
     std::vector<int64_t> nbs((size_t)F, 0);
     nbs[(size_t)stream] = nb;
     hipStream_t st = ctx->stream;
     if (nb) MSD_HIP(hipMemcpyAsync(drows + stream * 3 * ld, band_db, sizeof(double) * 3 * nb, hipMemcpyHostToDevice, st));
-    MSD_HIP(hipMemcpyAsync(s->d_aux, nbs.data(), sizeof(int64_t) * F, hipMemcpyHostToDevice, st));
+    MSD_HIP(hipMemcpyAsync(s->d_aux.get(), nbs.data(), sizeof(int64_t) * F, hipMemcpyHostToDevice, st));
     MSD_HIP(hipStreamSynchronize(st));  // nbs leaves scope below
-    if ((rc = ls_detect(s, drows, s->d_aux, nb, ld, dmet, dcap, s->d_aux + 2 * F, s->d_thr, s->P, s->d_over, s->P,
-                        s->d_status, s->d_aux + 3 * F, nullptr)))
+    if ((rc = ls_detect(s, drows, s->d_aux.get(), nb, ld, dmet, dcap, s->d_aux.get() + 2 * F, s->d_thr.get(), s->P, s->d_over.get(), s->P,
+                        s->d_status.get(), s->d_aux.get() + 3 * F, nullptr)))
         return rc;
     return ls_fetch(s, stream, dmet, dcap, out, count, nullptr, nullptr, thresholds, over, 0, status);
 }
@@ -1232,17 +1189,17 @@ int msd_live_session_push_samples(msd_live_session *s, int64_t stream, const voi
     const size_t es = dtype_size(s->dtype);
     void *dx, *dm;
     int rc;
-    if ((rc = ctx_scratch(ctx, 0, ((size_t)n * es + 255) / 256 * 256, &dx))) return rc;
-    if ((rc = ctx_scratch(ctx, 3, sizeof(msd_meteor) * (size_t)dcap * (size_t)F, &dm))) return rc;
+    if ((rc = ctx_scratch(ctx, SCRATCH_SAMPLES, ((size_t)n * es + 255) / 256 * 256, &dx))) return rc;
+    if ((rc = ctx_scratch(ctx, SCRATCH_DETECTIONS, sizeof(msd_meteor) * (size_t)dcap * (size_t)F, &dm))) return rc;
     msd_meteor *dmet = static_cast<msd_meteor *>(dm);
     std::vector<int64_t> meta((size_t)(2 * F), 0);  // off | len
     meta[(size_t)(F + stream)] = n;
     hipStream_t st = ctx->stream;
     if (n) MSD_HIP(hipMemcpyAsync(dx, x, (size_t)n * es, hipMemcpyHostToDevice, st));
-    MSD_HIP(hipMemcpyAsync(s->d_aux, meta.data(), sizeof(int64_t) * 2 * F, hipMemcpyHostToDevice, st));
+    MSD_HIP(hipMemcpyAsync(s->d_aux.get(), meta.data(), sizeof(int64_t) * 2 * F, hipMemcpyHostToDevice, st));
     MSD_HIP(hipStreamSynchronize(st));  // meta leaves scope below
-    if ((rc = msd_live_session_push_samples_dev(s, dx, s->d_aux, s->d_aux + F, n, dmet, dcap, s->d_aux + 2 * F,
-                                                s->d_aux + 3 * F, nullptr, nullptr, nullptr, 0, s->d_status)))
+    if ((rc = msd_live_session_push_samples_dev(s, dx, s->d_aux.get(), s->d_aux.get() + F, n, dmet, dcap, s->d_aux.get() + 2 * F,
+                                                s->d_aux.get() + 3 * F, nullptr, nullptr, nullptr, 0, s->d_status.get())))
         return rc;
     return ls_fetch(s, stream, dmet, dcap, out, count, new_blocks, band_db, thresholds, over, ld, status);
 }
@@ -1252,7 +1209,7 @@ int msd_live_session_state(msd_live_session *s, int64_t first, int64_t n, msd_li
     if (first < 0 || n < 0 || first + n > s->F) return fail(MSD_ERR_INVALID, "msd_live_session_state: streams out of range");
     if (!n) return MSD_OK;
     DeviceGuard g(s->ctx->device);
-    MSD_HIP(hipMemcpyAsync(out, s->d_state + first, sizeof(msd_live_stream_state) * (size_t)n, hipMemcpyDeviceToHost,
+    MSD_HIP(hipMemcpyAsync(out, s->d_state.get() + first, sizeof(msd_live_stream_state) * (size_t)n, hipMemcpyDeviceToHost,
                            s->ctx->stream));
     MSD_HIP(hipStreamSynchronize(s->ctx->stream));
     return MSD_OK;
@@ -1267,7 +1224,7 @@ int msd_live_session_history(msd_live_session *s, int64_t stream, double *out, i
     const int64_t m = S.retained < cap ? S.retained : cap;
     if (m <= 0) return MSD_OK;
     DeviceGuard g(s->ctx->device);
-    MSD_HIP(hipMemcpyAsync(out, s->d_hist + stream * (s->H + s->P), sizeof(double) * (size_t)m, hipMemcpyDeviceToHost,
+    MSD_HIP(hipMemcpyAsync(out, s->d_hist.get() + stream * (s->H + s->P), sizeof(double) * (size_t)m, hipMemcpyDeviceToHost,
                            s->ctx->stream));
     MSD_HIP(hipStreamSynchronize(s->ctx->stream));
     return MSD_OK;

@@ -4,10 +4,12 @@
 #include <hip/hip_runtime.h>
 
 #include <cstdint>
+#include <memory>
 #include <string>
 #include <vector>
 
 #include "../../include/msdsp.h"
+#include "dev_mem.h"
 
 namespace msd {
 
@@ -32,6 +34,57 @@ struct EventPair {
     int kernel;
 };
 
+// the context's scratch buffers, one per use (a call may hold several at once)
+enum ScratchSlot {
+    SCRATCH_SAMPLES = 0,    // the one file's samples (stage_one_file)
+    SCRATCH_META,           // its {offset, length}
+    SCRATCH_OUTPUT,         // the launcher's output before the read-back
+    SCRATCH_DETECTIONS,     // detector inputs, counters and detections / meteors
+    SCRATCH_WELCH_PSD,      // launch_welch_i8's PSD when the caller passes none
+    SCRATCH_LIVE_SEGMENTS,  // the live detector's per-segment scan states
+    SCRATCH_COUNT
+};
+
+// msd_iq_delta64_dev's caches, kept on the context
+struct RefineCache {
+    DevBuf<double2> w;  // twiddle table W^m (m < w_n), built once per frame length
+    int w_n = 0;
+    // the per-call tables staged in pinned memory (no stream sync), reusable once ev has passed
+    PinBuf pin;
+    hipEvent_t ev = nullptr;
+    // the tables of the last call as uploaded to `tables` (last_dev): a call with the same tables
+    // (every step of a stream of the same length) skips the two copies
+    std::vector<char> last;
+    const void *last_dev = nullptr;
+    DevBuf<char> tables;  // block table, rotations and ranges; last_dev is dropped where it grows
+    ~RefineCache() {
+        if (ev) (void)hipEventSynchronize(ev), (void)hipEventDestroy(ev);
+    }
+};
+
+// the int8-MFMA block step's tables: B fragments, column starts, lane twiddles, built once per
+// (frame length, bins)
+struct RefineI8Cache {
+    DevBuf<char> i8_tab;
+    uint64_t i8_key = 0;
+    // the exact (N, bins) they were built for: the hash only picks the candidate, a match needs
+    // these equal (a hash collision must not reuse another geometry's tables)
+    int i8_n = 0, i8_nk = 0;
+    int i8_km[16] = {};
+};
+
+// a guided chunk schedule on the device (guided_sched.h) for `total` items over `wgs` workgroups,
+// and the ticket the workgroups draw chunks by
+struct GuidedSched {
+    DevBuf<int64_t> bounds;
+    DevBuf<unsigned long long> ticket;
+    int64_t total = -1, wgs = -1, n = 0;  // n chunks: bounds[0 .. n]
+};
+// rebuilds and uploads the schedule when (total, wgs) differ from the last call's (the stream is
+// drained first), and always enqueues the ticket's reset on the stream
+int guided_sched_prepare(GuidedSched &s, hipStream_t stream, int64_t total, int64_t wgs, int64_t div, int64_t cmin,
+                         int64_t multiple, bool merge_short_tail);
+
 }  // namespace msd
 
 struct msd_ctx {
@@ -50,30 +103,11 @@ struct msd_ctx {
     std::vector<hipEvent_t> pool;         // reusable events
     double total_ms[msd::K_COUNT] = {};
     int64_t launches[msd::K_COUNT] = {};
-    // scratch device buffers for the host-pointer convenience entry points
-    // (slot 4: msd_iq_delta64_dev's block table, rotations and ranges; slot 5 unused since the
-    // post-FFT detrend's side records went, round 5)
-    void *scratch[8] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
-    size_t scratch_bytes[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-    // msd_iq_delta64_dev's twiddle table W^m (m < rf_w_n), built once per frame length
-    double2 *rf_w = nullptr;
-    int rf_w_n = 0;
-    // its per-call tables staged in pinned memory (no stream sync), reusable once rf_ev has passed
-    void *rf_pin = nullptr;
-    size_t rf_pin_bytes = 0;
-    hipEvent_t rf_ev = nullptr;
-    // the tables of the last call as uploaded to scratch slot 4 (rf_last_dev): a call with the same
-    // tables (every step of a stream of the same length) skips the two copies
-    std::vector<char> rf_last;
-    const void *rf_last_dev = nullptr;
-    // the int8-MFMA block step's tables (refine_i8.hip): B fragments, column starts, lane twiddles,
-    // built once per (frame length, bins)
-    void *i8_tab = nullptr;
-    uint64_t i8_key = 0;
-    // ...and the exact (N, bins) they were built for: the hash only picks the candidate, a match
-    // needs these equal (a hash collision must not reuse another geometry's tables)
-    int i8_n = 0, i8_nk = 0;
-    int i8_km[16] = {};
+    // scratch device buffers of the host-pointer convenience entry points (ctx_scratch)
+    msd::DevBuf<char> scratch[msd::SCRATCH_COUNT];
+    int64_t file_meta[2] = {0, 0};  // stage_one_file's {offset, length}: the source of its async copy
+    msd::RefineCache refine;       // msd_iq_delta64_dev (refine.hip)
+    msd::RefineI8Cache refine_i8;  // its int8-MFMA block step (refine_i8.hip)
     bool refine_goertzel = false;  // MSD_OPT_REFINE_GOERTZEL: int16 refinement on the float64 Goertzel
     bool block_goertzel = false;   // MSD_OPT_BLOCK_GOERTZEL: int16 block energies on the float64 Goertzel
     bool welch_goertzel = false;   // MSD_OPT_WELCH_GOERTZEL: int16 Welch band powers on the float64 Goertzel
@@ -92,16 +126,13 @@ struct msd_stft_plan {
     int detrend = 1;                             // 1 constant (scipy), 0 none (matplotlib mlab)
     int precision = MSD_F32;                     // arithmetic and output type: MSD_F32 or MSD_F64
     double scale = 0;
-    float *d_window = nullptr;   // [nperseg]  (MSD_F32 plans)
-    float2 *d_tw = nullptr;      // [M]    exp(-2*pi*i*m/M)
-    float2 *d_post = nullptr;    // [M+1]  exp(-2*pi*i*k/(2M))
-    double *d_window64 = nullptr;  // the same three in float64 (MSD_F64 plans)
-    double2 *d_tw64 = nullptr;
-    double2 *d_post64 = nullptr;
-    // stft1024_kernel's guided tile schedule (chunked, MSD_OPT_STFT_SCHED) and its ticket
-    int64_t *d_sched = nullptr;
-    int64_t sched_cap = 0, sched_total = -1, sched_wgs = -1, sched_n = 0;
-    unsigned long long *d_ticket = nullptr;
+    msd::DevBuf<float> d_window;   // [nperseg]  (MSD_F32 plans)
+    msd::DevBuf<float2> d_tw;      // [M]    exp(-2*pi*i*m/M)
+    msd::DevBuf<float2> d_post;    // [M+1]  exp(-2*pi*i*k/(2M))
+    msd::DevBuf<double> d_window64;  // the same three in float64 (MSD_F64 plans)
+    msd::DevBuf<double2> d_tw64;
+    msd::DevBuf<double2> d_post64;
+    msd::GuidedSched sched;  // stft1024_kernel's guided tile schedule (chunked, MSD_OPT_STFT_SCHED)
     // stft1024_kernel, integer samples: the frame mean m = tot / 1024 = a + b / 1024 (a = floor) comes
     // off as the exact integer a before the FFT and as b / 1024 times the window's DFT after it, which
     // is exact when that DFT vanishes past bin 1 (periodic Hann: W_0 = N/2, W_1 = -N/4).  win_dft01:
@@ -114,12 +145,9 @@ struct msd_stft_plan {
 struct msd_cstft_plan {
     msd_ctx *ctx = nullptr;
     int nperseg = 0, nfft = 0, hop = 0, detrend = 1;
-    float *d_win = nullptr;   // [nperseg] window x sqrt(scale)
-    float2 *d_tw = nullptr;   // [nfft] W_nfft^m
-    // cstft4096_kernel, DYN: the guided chunk schedule for (sched_total frames, sched_wgs workgroups) and the ticket
-    int64_t *d_sched = nullptr;
-    int64_t sched_cap = 0, sched_total = -1, sched_wgs = -1, sched_n = 0;
-    unsigned long long *d_ticket = nullptr;
+    msd::DevBuf<float> d_win;   // [nperseg] window x sqrt(scale)
+    msd::DevBuf<float2> d_tw;   // [nfft] W_nfft^m
+    msd::GuidedSched sched;     // cstft4096_kernel, DYN: the guided schedule of frame chunks
 };
 
 struct msd_block_plan {
@@ -128,18 +156,17 @@ struct msd_block_plan {
     int nfft = 0, L = 0;                  // L = min(B, nfft) samples used per block
     int band_lo = 0, band_hi = -1, noise_lo = 0, noise_hi = -1;
     int nbins = 0;                        // band bins + noise bins
-    double *d_window = nullptr;           // [L]
-    double2 *d_tw = nullptr;              // [nfft] exp(-2*pi*i*m/nfft)
-    int *d_bins = nullptr;                // [nbins] bin indices, band first
+    msd::DevBuf<double> d_window;         // [L]
+    msd::DevBuf<double2> d_tw;            // [nfft] exp(-2*pi*i*m/nfft)
+    msd::DevBuf<int> d_bins;              // [nbins] bin indices, band first
     // fast path (nbins <= 64): per bin {2cos th, cos th, -sin th}, then per (bin, 16-lane
     // segment) the rotation exp(-i th (seg*SPL + SPL - 1)) — host-computed in float64
     // long blocks (L > 4096, block_long_kernel): the per-bin constants alone; a lane's rotation comes
     // from d_tw
-    double *d_bconst = nullptr;
+    msd::DevBuf<double> d_bconst;
     int spl = 0;                          // samples per lane segment of the fast path / the long kernel
-    double2 *d_energy = nullptr;          // fast path: per block (band, noise) energy + 1e-12, grown
-    size_t energy_cap = 0;                // blocks d_energy holds
-    void *d_i8 = nullptr;                 // int16 blocks on the matrix cores (block_i8.hip): B fragments
+    msd::DevBuf<double2> d_energy;        // fast path: per block (band, noise) energy + 1e-12, grown
+    msd::DevBuf<char> d_i8;               // int16 blocks on the matrix cores (block_i8.hip): B fragments
                                           // + column constants, when block_i8_shape(L, nbins)
 };
 
@@ -148,11 +175,11 @@ struct msd_welch_plan {
     msd_welch_cfg cfg{};
     int nseg = 0, step = 0;       // segments per block, nperseg - noverlap
     int nslots = 0;               // bins computed per block (band ranges concatenated)
-    double *d_window = nullptr;   // [nperseg]
-    double *d_bins = nullptr;     // [nslots][4]: cos w, sin w, 2 cos w, doubling factor (1 or 2)
+    msd::DevBuf<double> d_window;   // [nperseg]
+    msd::DevBuf<double> d_bins;     // [nslots][4]: cos w, sin w, 2 cos w, doubling factor (1 or 2)
     // int16 samples on the matrix cores (welch_i8.hip): B fragments and doubling factors of the
-    // nct column tiles; null when the plan's shape does not take that path
-    void *d_i8 = nullptr;
+    // nct column tiles; empty when the plan's shape does not take that path
+    msd::DevBuf<char> d_i8;
     int i8_nct = 0;
     bool i8_pairs = false;  // the accumulators' digit sums fit int32 pairs (welch_i8_build)
 };
@@ -263,6 +290,16 @@ struct DeviceGuard {
     }
 };
 
+// the destroy entry point of a plan or session: its work on the context's stream ends, then its
+// members free their memory
+template <typename P>
+void destroy_plan(P *p) {
+    if (!p) return;
+    DeviceGuard g(p->ctx->device);
+    (void)hipStreamSynchronize(p->ctx->stream);
+    delete p;
+}
+
 // scoped timing of one kernel launch on ctx->stream
 struct KernelTimer {
     msd_ctx *ctx;
@@ -282,8 +319,12 @@ __device__ __forceinline__ float vgpr_f(float c) {
     return r;
 }
 
-// scratch buffer i of the context grown to at least `bytes`
-int ctx_scratch(msd_ctx *ctx, int slot, size_t bytes, void **out);
+// the context's scratch buffer `slot` grown to at least `bytes`
+int ctx_scratch(msd_ctx *ctx, ScratchSlot slot, size_t bytes, void **out);
+// one file of a host-pointer entry point on the device: the n samples (`bytes` of them) into the
+// samples slot and {0, n} into the meta slot, both copies enqueued on the context's stream;
+// *doff, *doff + 1 are the launchers' off and len
+int stage_one_file(msd_ctx *ctx, const void *x, size_t bytes, int64_t n, const void **dx, const int64_t **doff);
 
 // launchers (defined in the kernel translation units)
 // out: float32 or float64 [nfiles][K][ld] by the plan's precision

@@ -366,7 +366,8 @@ int msd_iq_delta64_sums_dev(msd_ctx *ctx, const void *x, int32_t dtype, int64_t 
     hipStream_t st = ctx->stream;
     // W^m (m < N): built and uploaded once per frame length (N sin / cos on the host cost
     // ~0.2 ms, more than the refinement's other host work), kept on the context
-    if (ctx->rf_w_n != N) {
+    RefineCache &cache = ctx->refine;
+    if (cache.w_n != N) {
         std::vector<double2> W(N);
         for (int m = 0; m < N; ++m) {  // W^m = cos - i sin of 2 pi m / N, each within ~0.5 ulp
             long double c, sn;
@@ -374,14 +375,11 @@ int msd_iq_delta64_sums_dev(msd_ctx *ctx, const void *x, int32_t dtype, int64_t 
             W[m] = make_double2((double)c, -(double)sn);
         }
         MSD_HIP(hipStreamSynchronize(st));
-        if (ctx->rf_w) MSD_HIP(hipFree(ctx->rf_w));
-        ctx->rf_w = nullptr;
-        ctx->rf_w_n = 0;
-        MSD_HIP(hipMalloc(&ctx->rf_w, sizeof(double2) * N));
-        MSD_HIP(hipMemcpy(ctx->rf_w, W.data(), sizeof(double2) * N, hipMemcpyHostToDevice));
-        ctx->rf_w_n = N;
+        cache.w_n = 0;
+        if (int r = cache.w.upload(W.data(), N, "msd_iq_delta64_dev: twiddles")) return r;
+        cache.w_n = N;
     }
-    const double2 *Wd = ctx->rf_w;
+    const double2 *Wd = cache.w.get();
     // per call: the per-bin block rotations rot[b][j] = W^{k_b j D} (j < R), and the ranges
     const int R = G.R;
     std::vector<double2> rt((size_t)K.nk * R);
@@ -395,11 +393,15 @@ int msd_iq_delta64_sums_dev(msd_ctx *ctx, const void *x, int32_t dtype, int64_t 
     const size_t nb_blk = (sizeof(double2) * (size_t)nblocks * (K.nk + 2) + 255) / 256 * 256;
     const size_t nb_rot = (sizeof(double2) * rt.size() + 255) / 256 * 256;
     const size_t nb_meta = sizeof(int64_t) * (4 * (size_t)nranges + 2);
-    void *d = nullptr;
-    if (int rc = ctx_scratch(ctx, 4, nb_blk + nb_rot + nb_meta, &d)) return rc;  // grown once, kept
-    auto *blk = static_cast<double2 *>(d);
-    auto *rot = reinterpret_cast<double2 *>(static_cast<char *>(d) + nb_blk);
-    auto *meta = reinterpret_cast<int64_t *>(static_cast<char *>(d) + nb_blk + nb_rot);
+    const size_t nb_tab = std::max<size_t>(nb_blk + nb_rot + nb_meta, 4096);
+    if (cache.tables.size() < nb_tab) {  // grown once, kept
+        cache.last_dev = nullptr;  // a new block (perhaps at the old address) holds no uploaded tables
+        if (int r = cache.tables.grow(nb_tab, st, "msd_iq_delta64_dev: tables")) return r;
+    }
+    char *d = cache.tables.get();
+    auto *blk = reinterpret_cast<double2 *>(d);
+    auto *rot = reinterpret_cast<double2 *>(d + nb_blk);
+    auto *meta = reinterpret_cast<int64_t *>(d + nb_blk + nb_rot);
     std::vector<int64_t> hm;
     hm.insert(hm.end(), fstart.begin(), fstart.end());
     hm.insert(hm.end(), fcs.begin(), fcs.end());
@@ -409,34 +411,27 @@ int msd_iq_delta64_sums_dev(msd_ctx *ctx, const void *x, int32_t dtype, int64_t 
                   *d_bcs = meta + 3 * nranges + 1;
     // both tables through a pinned staging block (the copies are truly async, so the call returns
     // while the kernels run); the previous call's copies have left it once its event has passed.
-    // The same tables as the last call's, still in the same scratch block, are not copied again:
+    // The same tables as the last call's, still in the same block, are not copied again:
     // in the C5 step the two copies sat between the spectrogram's end and the delta's start.
     const size_t b_rt = sizeof(double2) * rt.size(), b_hm = sizeof(int64_t) * hm.size();
-    const bool same = ctx->rf_last_dev == d && ctx->rf_last.size() == b_rt + b_hm &&
-                      !std::memcmp(ctx->rf_last.data(), rt.data(), b_rt) &&
-                      !std::memcmp(ctx->rf_last.data() + b_rt, hm.data(), b_hm);
+    const bool same = cache.last_dev == d && cache.last.size() == b_rt + b_hm &&
+                      !std::memcmp(cache.last.data(), rt.data(), b_rt) &&
+                      !std::memcmp(cache.last.data() + b_rt, hm.data(), b_hm);
     hipError_t e = hipSuccess;
     if (!same) {
-        ctx->rf_last_dev = nullptr;  // set again once both copies are enqueued
-        if (!ctx->rf_ev) MSD_HIP(hipEventCreateWithFlags(&ctx->rf_ev, hipEventDisableTiming));
-        else MSD_HIP(hipEventSynchronize(ctx->rf_ev));
-        if (ctx->rf_pin_bytes < b_rt + b_hm) {
-            if (ctx->rf_pin) MSD_HIP(hipHostFree(ctx->rf_pin));
-            ctx->rf_pin = nullptr;
-            ctx->rf_pin_bytes = 0;
-            const size_t want = std::max<size_t>(b_rt + b_hm, 4096);
-            MSD_HIP(hipHostMalloc(&ctx->rf_pin, want, hipHostMallocDefault));
-            ctx->rf_pin_bytes = want;
-        }
-        char *pin = static_cast<char *>(ctx->rf_pin);
+        cache.last_dev = nullptr;  // set again once both copies are enqueued
+        if (!cache.ev) MSD_HIP(hipEventCreateWithFlags(&cache.ev, hipEventDisableTiming));
+        else MSD_HIP(hipEventSynchronize(cache.ev));
+        if (int r = cache.pin.grow(std::max<size_t>(b_rt + b_hm, 4096), "msd_iq_delta64_dev: staging")) return r;
+        char *pin = static_cast<char *>(cache.pin.get());
         std::memcpy(pin, rt.data(), b_rt);
         std::memcpy(pin + b_rt, hm.data(), b_hm);
         e = hipMemcpyAsync(rot, pin, b_rt, hipMemcpyHostToDevice, st);
         if (e == hipSuccess) e = hipMemcpyAsync(meta, pin + b_rt, b_hm, hipMemcpyHostToDevice, st);
-        if (e == hipSuccess) e = hipEventRecord(ctx->rf_ev, st);
+        if (e == hipSuccess) e = hipEventRecord(cache.ev, st);
         if (e == hipSuccess) {
-            ctx->rf_last.assign(pin, pin + b_rt + b_hm);
-            ctx->rf_last_dev = d;
+            cache.last.assign(pin, pin + b_rt + b_hm);
+            cache.last_dev = d;
         }
     }
     // int16 blocks of 1024 samples: the exact integer DFT on the matrix cores (refine_i8.hip), its

@@ -303,8 +303,9 @@ int launch_refine_i8(msd_ctx *ctx, const int16_t *x, const RefineGeom &G, const 
     const size_t nb_init = sizeof(int) * (size_t)NT * 16;
     const size_t nb_tw = sizeof(double2) * (size_t)(1 + (NT - 6)) * I8_SB * 16;
     const size_t nb_all = nb_frag + nb_init + nb_tw;
-    bool same = ctx->i8_tab && ctx->i8_key == key && ctx->i8_n == N && ctx->i8_nk == nk;
-    for (int b = 0; same && b < nk; ++b) same = ctx->i8_km[b] == K.km[b];
+    RefineI8Cache &c8 = ctx->refine_i8;
+    bool same = c8.i8_tab.get() && c8.i8_key == key && c8.i8_n == N && c8.i8_nk == nk;
+    for (int b = 0; same && b < nk; ++b) same = c8.i8_km[b] == K.km[b];
     if (!same) {
         // column (t, c) -> (bin, part, digit), or -1
         auto colmap = [&](int t, int cc, int &bin, int &part, int &dig) {
@@ -376,17 +377,14 @@ int launch_refine_i8(msd_ctx *ctx, const int16_t *x, const RefineGeom &G, const 
                 }
         DeviceGuard gd(ctx->device);
         MSD_HIP(hipStreamSynchronize(ctx->stream));
-        if (ctx->i8_tab) MSD_HIP(hipFree(ctx->i8_tab));
-        ctx->i8_tab = nullptr;
-        ctx->i8_key = 0;
-        MSD_HIP(hipMalloc(&ctx->i8_tab, nb_all));
-        MSD_HIP(hipMemcpy(ctx->i8_tab, tab.data(), nb_all, hipMemcpyHostToDevice));
-        ctx->i8_key = key;
-        ctx->i8_n = N;
-        ctx->i8_nk = nk;
-        for (int b = 0; b < nk; ++b) ctx->i8_km[b] = K.km[b];
+        c8.i8_key = 0;
+        if (int rc = c8.i8_tab.upload(tab.data(), nb_all, "refine_i8: tables")) return rc;
+        c8.i8_key = key;
+        c8.i8_n = N;
+        c8.i8_nk = nk;
+        for (int b = 0; b < nk; ++b) c8.i8_km[b] = K.km[b];
     }
-    const char *tb = static_cast<const char *>(ctx->i8_tab);
+    const char *tb = c8.i8_tab.get();
     const v4i *d_frag = reinterpret_cast<const v4i *>(tb);
     const int *d_init = reinterpret_cast<const int *>(tb + nb_frag);
     const double2 *d_tw = reinterpret_cast<const double2 *>(tb + nb_frag + nb_init);

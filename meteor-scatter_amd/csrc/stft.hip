@@ -267,7 +267,7 @@ int launch_t(msd_stft_plan *p, const void *x, const int64_t *off, const int64_t 
     if (blocks > 0x7fffffffLL) return fail(MSD_ERR_UNSUPPORTED, "stft: grid too large");
     hipLaunchKernelGGL(kern, dim3((unsigned)blocks), dim3(NW * 64), G::LDS_BYTES, p->ctx->stream,
                        static_cast<const T *>(x), off, len, tiles, p->hop, static_cast<float>(p->scale),
-                       p->detrend, p->d_window, p->d_tw, p->d_post, out, ld);
+                       p->detrend, p->d_window.get(), p->d_tw.get(), p->d_post.get(), out, ld);
     MSD_HIP(hipGetLastError());
     return MSD_OK;
 }

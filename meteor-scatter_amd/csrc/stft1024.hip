@@ -634,42 +634,20 @@ int launch_fast_t(msd_stft_plan *p, const void *x, const int64_t *off, const int
         auto dkern = wide ? (sh ? stft1024_kernel<T, 1, PairIO<T>::kInt, true> : stft1024_kernel<T, 1, false, true>)
                           : (sh ? stft1024_kernel<T, 0, PairIO<T>::kInt, true> : stft1024_kernel<T, 0, false, true>);
         if (int rc = ensure_dyn_lds(reinterpret_cast<const void *>(dkern), F_LDS)) return rc;
-        if (p->sched_total != ntiles || p->sched_wgs != wgs) {
-            // guided: each chunk 1 / (div * wgs) of what is left, at least cmin tiles
-            constexpr int64_t cmin = 2, div = 2;
-            std::vector<int64_t> st(1, 0);
-            for (int64_t pos = 0; pos < ntiles;) {
-                const int64_t sz = std::max<int64_t>((ntiles - pos) / (div * wgs), cmin);
-                pos = std::min(ntiles, pos + sz);
-                if (ntiles - pos > 0 && ntiles - pos < cmin) pos = ntiles;  // no chunk below cmin at the end
-                st.push_back(pos);
-            }
-            MSD_HIP(hipStreamSynchronize(p->ctx->stream));
-            if ((int64_t)st.size() > p->sched_cap) {
-                if (p->d_sched) MSD_HIP(hipFree(p->d_sched));
-                p->d_sched = nullptr;
-                p->sched_cap = 0;
-                MSD_HIP(hipMalloc(&p->d_sched, sizeof(int64_t) * st.size()));
-                p->sched_cap = (int64_t)st.size();
-            }
-            if (!p->d_ticket) MSD_HIP(hipMalloc(&p->d_ticket, sizeof(unsigned long long)));
-            MSD_HIP(hipMemcpy(p->d_sched, st.data(), sizeof(int64_t) * st.size(), hipMemcpyHostToDevice));
-            p->sched_total = ntiles;
-            p->sched_wgs = wgs;
-            p->sched_n = (int64_t)st.size() - 1;
-        }
-        MSD_HIP(hipMemsetAsync(p->d_ticket, 0, sizeof(unsigned long long), p->ctx->stream));
+        // guided: each chunk 1 / (2 wgs) of what is left, at least 2 tiles, none below that at the end
+        if (int rc = guided_sched_prepare(p->sched, p->ctx->stream, ntiles, wgs, 2, 2, 1, true)) return rc;
         hipLaunchKernelGGL(dkern, dim3((unsigned)wgs), dim3(F_NW * 64), F_LDS, p->ctx->stream, static_cast<const T *>(x),
-                           off, len, tiles_per_file, ntiles, (int64_t)0, p->hop, ws, p->detrend, p->d_window, p->d_tw,
-                           p->d_post, out, ld, p->d_sched, p->sched_n, p->d_ticket, dcw0, dcw1);
+                           off, len, tiles_per_file, ntiles, (int64_t)0, p->hop, ws, p->detrend, p->d_window.get(),
+                           p->d_tw.get(), p->d_post.get(), out, ld, p->sched.bounds.get(), p->sched.n,
+                           p->sched.ticket.get(), dcw0, dcw1);
         MSD_HIP(hipGetLastError());
         return MSD_OK;
     }
     const int64_t per = (ntiles + wgs - 1) / wgs;
     wgs = (ntiles + per - 1) / per;
     hipLaunchKernelGGL(kern, dim3((unsigned)wgs), dim3(F_NW * 64), F_LDS, p->ctx->stream, static_cast<const T *>(x),
-                       off, len, tiles_per_file, ntiles, per, p->hop, ws, p->detrend, p->d_window, p->d_tw, p->d_post,
-                       out, ld, nullptr, (int64_t)0, nullptr, dcw0, dcw1);
+                       off, len, tiles_per_file, ntiles, per, p->hop, ws, p->detrend, p->d_window.get(), p->d_tw.get(),
+                       p->d_post.get(), out, ld, nullptr, (int64_t)0, nullptr, dcw0, dcw1);
     MSD_HIP(hipGetLastError());
     return MSD_OK;
 }

@@ -282,11 +282,10 @@ int launch_any_t(msd_stft_plan *p, const void *x, const int64_t *off, const int6
     int logM = 0;
     while ((1 << logM) < M) ++logM;
     // the plan keeps its window and twiddles in the precision it computes in
-    const R *win = static_cast<const R *>(p->precision == MSD_F64 ? (const void *)p->d_window64
-                                                                  : (const void *)p->d_window);
-    const C *tw = static_cast<const C *>(p->precision == MSD_F64 ? (const void *)p->d_tw64 : (const void *)p->d_tw);
-    const C *post =
-        static_cast<const C *>(p->precision == MSD_F64 ? (const void *)p->d_post64 : (const void *)p->d_post);
+    const bool f64 = p->precision == MSD_F64;
+    const R *win = static_cast<const R *>(f64 ? (const void *)p->d_window64.get() : (const void *)p->d_window.get());
+    const C *tw = static_cast<const C *>(f64 ? (const void *)p->d_tw64.get() : (const void *)p->d_tw.get());
+    const C *post = static_cast<const C *>(f64 ? (const void *)p->d_post64.get() : (const void *)p->d_post.get());
     hipLaunchKernelGGL(kern, dim3((unsigned)ld, (unsigned)nfiles), dim3(SA_THREADS), lds, p->ctx->stream,
                        static_cast<const T *>(x), off, len, p->nperseg, p->hop, M, logM, static_cast<R>(p->scale),
                        p->detrend, win, tw, post, out, ld);

@@ -46,40 +46,40 @@ struct msd_stream_plan {
     int64_t n_total = 0, frame0 = 0, n_local = 0;
     int64_t n_tail = 0, n_head = 0, head_cap = 0;
     int64_t seg_len = 0, nseg = 0, cap = 0;
-    double *d_x = nullptr;      // [n_tail | n_local | head_cap] delta of the stream around the shard
-    double *d_fresh = nullptr;  // [n_local]
-    double *d_thr = nullptr;    // [n_local] thresholds used (scan output)
-    void *d_state = nullptr;    // in[nseg], out[nseg] states
-    int32_t *d_active = nullptr;  // [nseg] + changed counter + overflow flag
-    msd_det *d_runs = nullptr;  // [nseg][cap]
-    int32_t *d_nruns = nullptr; // [nseg]
-    double *d_margin = nullptr; // [nseg]
-    msd_det *d_out = nullptr;   // compacted runs [nseg*cap]
-    int64_t *d_count = nullptr;
-    int64_t *d_pos = nullptr;   // [nseg] runs emitted before each segment
-    double *d_chunks = nullptr; // chunk sums [nchunk] + the local path's mean, thr0
-    int4 *d_prog = nullptr;     // fresh-threshold leaf records for windows of exactly W frames
-    int32_t *d_need = nullptr;  // [ntiles] a scan used fresh thresholds in the tile
-    int32_t *d_done = nullptr;  // [ntiles] the tile's exact thresholds are computed (+1: counter)
-    double2 *d_pre = nullptr;   // [nblk + 1] prefix sums of x, x^2 (the predictor)
+    msd::DevBuf<double> d_x;      // [n_tail | n_local | head_cap] delta of the stream around the shard
+    msd::DevBuf<double> d_fresh;  // [n_local]
+    msd::DevBuf<double> d_thr;    // [n_local] thresholds used (scan output)
+    msd::DevBuf<char> d_state;    // in[nseg], out[nseg] states
+    msd::DevBuf<int32_t> d_active;  // [nseg] + changed counter + overflow flag
+    msd::DevBuf<msd_det> d_runs;  // [nseg][cap]
+    msd::DevBuf<int32_t> d_nruns; // [nseg]
+    msd::DevBuf<double> d_margin; // [nseg]
+    msd::DevBuf<msd_det> d_out;   // compacted runs [nseg*cap]
+    msd::DevBuf<int64_t> d_count;
+    msd::DevBuf<int64_t> d_pos;   // [nseg] runs emitted before each segment
+    msd::DevBuf<double> d_chunks; // chunk sums [nchunk] + the local path's mean, thr0
+    msd::DevBuf<int4> d_prog;     // fresh-threshold leaf records for windows of exactly W frames
+    msd::DevBuf<int32_t> d_need;  // [ntiles] a scan used fresh thresholds in the tile
+    msd::DevBuf<int32_t> d_done;  // [ntiles] the tile's exact thresholds are computed (+1: counter)
+    msd::DevBuf<double2> d_pre;   // [nblk + 1] prefix sums of x, x^2 (the predictor)
     // decisions-only mode (msd_stream_set_exact_thresholds(plan, 0)): exact thresholds per frame,
     // only where a decision or a held threshold depends on them
-    double *d_eps = nullptr;      // [n_local] bound on |predicted - numpy threshold|
-    uint8_t *d_exact = nullptr;   // [n_local] fresh[j] is numpy-exact
-    int32_t *d_list = nullptr;    // [n_local] frames the last marking pass needs exact
+    msd::DevBuf<double> d_eps;      // [n_local] bound on |predicted - numpy threshold|
+    msd::DevBuf<uint8_t> d_exact;   // [n_local] fresh[j] is numpy-exact
+    msd::DevBuf<int32_t> d_list;    // [n_local] frames the last marking pass needs exact
     bool decide = false;
     // certification against the float64 reference (msd_stream_set_certify): a bound on |delta -
     // delta_ref| per frame, the thresholds' error from it, and per segment the decisions the bounds
     // cannot settle
     bool certify = false;
-    double *d_ed = nullptr;       // [n_tail | n_local | head_cap] delta error bound (as d_x)
-    double *d_terr = nullptr;     // [n_local] bound on |numpy threshold(delta) - numpy threshold(delta_ref)|
-    double2 *d_pre_e = nullptr;   // [nblk + 1] prefix sums of (ed, ed^2)
-    longlong2 *d_unc = nullptr;   // [nseg][UCAP] uncertain decisions {local frame, threshold source frame}
-    int32_t *d_ucnt = nullptr;    // [nseg] uncertain decisions of the segment's last scan
-    double2 *d_slack = nullptr;   // [nseg] min over the segment of |delta - thr| - (ed + threshold error), max of
+    msd::DevBuf<double> d_ed;       // [n_tail | n_local | head_cap] delta error bound (as d_x)
+    msd::DevBuf<double> d_terr;     // [n_local] bound on |numpy threshold(delta) - numpy threshold(delta_ref)|
+    msd::DevBuf<double2> d_pre_e;   // [nblk + 1] prefix sums of (ed, ed^2)
+    msd::DevBuf<longlong2> d_unc;   // [nseg][UCAP] uncertain decisions {local frame, threshold source frame}
+    msd::DevBuf<int32_t> d_ucnt;    // [nseg] uncertain decisions of the segment's last scan
+    msd::DevBuf<double2> d_slack;   // [nseg] min over the segment of |delta - thr| - (ed + threshold error), max of
                                   // ed + threshold error
-    double2 *d_esum = nullptr;    // [nchunk + 1] per-chunk (sum ed, sum ed^2), then the shard's total
+    msd::DevBuf<double2> d_esum;    // [nchunk + 1] per-chunk (sum ed, sum ed^2), then the shard's total
     double terr0 = 0.0;           // bound for thr0 (whole-stream mean + k std)
     int64_t ntiles = 0, nblk = 0;
     int nleaf = 0;
@@ -97,9 +97,8 @@ struct msd_stream_plan {
     // sums): the copies are asynchronous DMA and a decision point costs one stream sync, where a
     // pageable destination costs a staged, host-synchronous copy each (≈ 18 µs per copy in the C5
     // step's timeline)
-    void *h_pin = nullptr;
-    void *h_cert = nullptr;  // pinned staging of msd_stream_certificate
-    size_t h_cert_bytes = 0;
+    msd::PinBuf h_pin;
+    msd::PinBuf h_cert;  // pinned staging of msd_stream_certificate
 };
 
 namespace msd {
@@ -1207,11 +1206,11 @@ __global__ void db_kernel(const double *__restrict__ x, int64_t x0, msd_det *__r
 
 using namespace msd;
 
-static PinHdr *pin_hdr(msd_stream_plan *p) { return static_cast<PinHdr *>(p->h_pin); }
+static PinHdr *pin_hdr(msd_stream_plan *p) { return static_cast<PinHdr *>(p->h_pin.get()); }
 static double *pin_margin(msd_stream_plan *p) { return reinterpret_cast<double *>(pin_hdr(p) + 1); }
 static double *pin_chunks(msd_stream_plan *p) { return pin_margin(p) + (p->nseg > 0 ? p->nseg : 1); }
-static SState *st_in(msd_stream_plan *p) { return reinterpret_cast<SState *>(p->d_state); }
-static SState *st_out(msd_stream_plan *p) { return reinterpret_cast<SState *>(p->d_state) + p->nseg; }
+static SState *st_in(msd_stream_plan *p) { return reinterpret_cast<SState *>(p->d_state.get()); }
+static SState *st_out(msd_stream_plan *p) { return reinterpret_cast<SState *>(p->d_state.get()) + p->nseg; }
 
 extern "C" {
 
@@ -1257,7 +1256,7 @@ int msd_stream_plan_create(msd_ctx *ctx, const msd_det_cfg *cfg, int64_t n_total
         return fail(MSD_ERR_INVALID, "msd_stream_plan_create: negative block counts");
     *out = nullptr;
     DeviceGuard g(ctx->device);
-    auto *p = new msd_stream_plan();
+    auto p = std::make_unique<msd_stream_plan>();
     p->ctx = ctx;
     p->cfg = *cfg;
     p->n_total = n_total;
@@ -1274,90 +1273,60 @@ int msd_stream_plan_create(msd_ctx *ctx, const msd_det_cfg *cfg, int64_t n_total
     const int64_t nseg1 = p->nseg > 0 ? p->nseg : 1;
     const int64_t nl1 = n_local > 0 ? n_local : 1;
     const int64_t nchunk = n_local / CHUNK + 2;
-    auto cleanup = [&](hipError_t e, const char *what) {
-        msd_stream_plan_destroy(p);
-        return hip_fail(e, what);
-    };
-    hipError_t e;
-    if ((e = hipMalloc(&p->d_x, sizeof(double) * (p->n_tail + nl1 + p->head_cap))) != hipSuccess)
-        return cleanup(e, "hipMalloc stream x");
-    if ((e = hipMalloc(&p->d_fresh, sizeof(double) * nl1)) != hipSuccess) return cleanup(e, "hipMalloc fresh");
-    if ((e = hipMalloc(&p->d_thr, sizeof(double) * nl1)) != hipSuccess) return cleanup(e, "hipMalloc thr");
-    if ((e = hipMalloc(&p->d_state, sizeof(SState) * 2 * nseg1)) != hipSuccess) return cleanup(e, "hipMalloc state");
-    if ((e = hipMalloc(&p->d_active, sizeof(int32_t) * (nseg1 + 2))) != hipSuccess)
-        return cleanup(e, "hipMalloc active");
-    if ((e = hipMalloc(&p->d_runs, sizeof(msd_det) * nseg1 * cap_per_seg)) != hipSuccess)
-        return cleanup(e, "hipMalloc runs");
-    if ((e = hipMalloc(&p->d_out, sizeof(msd_det) * nseg1 * cap_per_seg)) != hipSuccess)
-        return cleanup(e, "hipMalloc out");
-    if ((e = hipMalloc(&p->d_nruns, sizeof(int32_t) * nseg1)) != hipSuccess) return cleanup(e, "hipMalloc nruns");
-    if ((e = hipMalloc(&p->d_margin, sizeof(double) * nseg1)) != hipSuccess) return cleanup(e, "hipMalloc margin");
-    if ((e = hipMalloc(&p->d_count, sizeof(int64_t))) != hipSuccess) return cleanup(e, "hipMalloc count");
-    if ((e = hipMalloc(&p->d_pos, sizeof(int64_t) * nseg1)) != hipSuccess) return cleanup(e, "hipMalloc pos");
-    if ((e = hipMalloc(&p->d_chunks, sizeof(double) * (nchunk + 2))) != hipSuccess)
-        return cleanup(e, "hipMalloc chunks");
-    if ((e = hipHostMalloc(&p->h_pin, sizeof(PinHdr) + sizeof(double) * (nseg1 + nchunk + 4), hipHostMallocDefault)) !=
-        hipSuccess)
-        return cleanup(e, "hipHostMalloc stream readbacks");
     p->ntiles = (nl1 + FR_FRAMES - 1) / FR_FRAMES;
     p->nblk = (p->n_tail + nl1 + p->head_cap) / PB + 1;
-    if ((e = hipMalloc(&p->d_need, sizeof(int32_t) * p->ntiles)) != hipSuccess) return cleanup(e, "hipMalloc need");
-    if ((e = hipMalloc(&p->d_done, sizeof(int32_t) * (p->ntiles + 1))) != hipSuccess)
-        return cleanup(e, "hipMalloc done");
-    if ((e = hipMalloc(&p->d_pre, sizeof(double2) * (p->nblk + 1))) != hipSuccess) return cleanup(e, "hipMalloc pre");
-    if ((e = hipMalloc(&p->d_eps, sizeof(double) * nl1)) != hipSuccess) return cleanup(e, "hipMalloc eps");
-    if ((e = hipMalloc(&p->d_exact, nl1)) != hipSuccess) return cleanup(e, "hipMalloc exact");
-    if ((e = hipMalloc(&p->d_list, sizeof(int32_t) * nl1)) != hipSuccess) return cleanup(e, "hipMalloc list");
-    // certification buffers (used after msd_stream_set_certify); ed starts at 0 (delta exact)
     const int64_t xl = p->n_tail + nl1 + p->head_cap;
-    if ((e = hipMalloc(&p->d_ed, sizeof(double) * xl)) != hipSuccess) return cleanup(e, "hipMalloc ed");
-    if ((e = hipMemset(p->d_ed, 0, sizeof(double) * xl)) != hipSuccess) return cleanup(e, "hipMemset ed");
-    if ((e = hipMalloc(&p->d_terr, sizeof(double) * nl1)) != hipSuccess) return cleanup(e, "hipMalloc terr");
-    if ((e = hipMalloc(&p->d_pre_e, sizeof(double2) * (p->nblk + 1))) != hipSuccess)
-        return cleanup(e, "hipMalloc pre_e");
-    if ((e = hipMalloc(&p->d_unc, sizeof(longlong2) * nseg1 * UCAP)) != hipSuccess) return cleanup(e, "hipMalloc unc");
-    if ((e = hipMalloc(&p->d_ucnt, sizeof(int32_t) * nseg1)) != hipSuccess) return cleanup(e, "hipMalloc ucnt");
-    if ((e = hipMemset(p->d_ucnt, 0, sizeof(int32_t) * nseg1)) != hipSuccess) return cleanup(e, "hipMemset ucnt");
-    if ((e = hipMalloc(&p->d_slack, sizeof(double2) * nseg1)) != hipSuccess) return cleanup(e, "hipMalloc slack");
-    if ((e = hipMalloc(&p->d_esum, sizeof(double2) * (xl / CHUNK + 2))) != hipSuccess)
-        return cleanup(e, "hipMalloc esum");
-    if (W > 0) {
+    int rc;
+    (rc = p->d_x.alloc(xl, "stream plan: x")) ||
+        (rc = p->d_fresh.alloc(nl1, "stream plan: fresh")) ||
+        (rc = p->d_thr.alloc(nl1, "stream plan: thr")) ||
+        (rc = p->d_state.alloc(sizeof(SState) * 2 * nseg1, "stream plan: state")) ||
+        (rc = p->d_active.alloc(nseg1 + 2, "stream plan: active")) ||
+        (rc = p->d_runs.alloc(nseg1 * cap_per_seg, "stream plan: runs")) ||
+        (rc = p->d_out.alloc(nseg1 * cap_per_seg, "stream plan: out")) ||
+        (rc = p->d_nruns.alloc(nseg1, "stream plan: nruns")) ||
+        (rc = p->d_margin.alloc(nseg1, "stream plan: margin")) ||
+        (rc = p->d_count.alloc(1, "stream plan: count")) ||
+        (rc = p->d_pos.alloc(nseg1, "stream plan: pos")) ||
+        (rc = p->d_chunks.alloc(nchunk + 2, "stream plan: chunks")) ||
+        (rc = p->h_pin.alloc(sizeof(PinHdr) + sizeof(double) * (nseg1 + nchunk + 4), "stream plan: pinned readbacks")) ||
+        (rc = p->d_need.alloc(p->ntiles, "stream plan: need")) ||
+        (rc = p->d_done.alloc(p->ntiles + 1, "stream plan: done")) ||
+        (rc = p->d_pre.alloc(p->nblk + 1, "stream plan: pre")) ||
+        (rc = p->d_eps.alloc(nl1, "stream plan: eps")) ||
+        (rc = p->d_exact.alloc(nl1, "stream plan: exact")) ||
+        (rc = p->d_list.alloc(nl1, "stream plan: list")) ||
+        // certification buffers (used after msd_stream_set_certify); ed starts at 0 (delta exact)
+        (rc = p->d_ed.alloc(xl, "stream plan: ed")) || (rc = p->d_ed.zero()) ||
+        (rc = p->d_terr.alloc(nl1, "stream plan: terr")) ||
+        (rc = p->d_pre_e.alloc(p->nblk + 1, "stream plan: pre_e")) ||
+        (rc = p->d_unc.alloc(nseg1 * UCAP, "stream plan: unc")) ||
+        (rc = p->d_ucnt.alloc(nseg1, "stream plan: ucnt")) || (rc = p->d_ucnt.zero()) ||
+        (rc = p->d_slack.alloc(nseg1, "stream plan: slack")) ||
+        (rc = p->d_esum.alloc(xl / CHUNK + 2, "stream plan: esum"));
+    if (!rc && W > 0) {
         std::vector<LeafRec> prog;  // np_program.h; LeafRec has int4's layout
         static_assert(sizeof(LeafRec) == sizeof(int4), "leaf record layout");
         build_program(W, prog);
         p->nleaf = (int)prog.size();
-        if ((e = hipMalloc(&p->d_prog, sizeof(int4) * prog.size())) != hipSuccess) return cleanup(e, "hipMalloc prog");
-        if ((e = hipMemcpy(p->d_prog, prog.data(), sizeof(int4) * prog.size(), hipMemcpyHostToDevice)) != hipSuccess)
-            return cleanup(e, "hipMemcpy prog");
+        rc = p->d_prog.upload(reinterpret_cast<const int4 *>(prog.data()), prog.size(), "stream plan: prog");
     }
-    *out = p;
+    if (rc) return rc;
+    *out = p.release();
     return MSD_OK;
 }
 
-void msd_stream_plan_destroy(msd_stream_plan *p) {
-    if (!p) return;
-    DeviceGuard g(p->ctx->device);
-    hipStreamSynchronize(p->ctx->stream);
-    void *bufs[] = {p->d_x, p->d_fresh, p->d_thr, p->d_state, p->d_active, p->d_runs, p->d_out, p->d_nruns,
-                    p->d_margin, p->d_count, p->d_pos, p->d_chunks, p->d_prog, p->d_need, p->d_done, p->d_pre,
-                    p->d_eps, p->d_exact, p->d_list, p->d_ed, p->d_terr, p->d_pre_e, p->d_unc, p->d_ucnt,
-                    p->d_slack, p->d_esum};
-    for (void *b : bufs)
-        if (b) hipFree(b);
-    if (p->h_pin) hipHostFree(p->h_pin);
-    if (p->h_cert) hipHostFree(p->h_cert);
-    delete p;
-}
+void msd_stream_plan_destroy(msd_stream_plan *p) { destroy_plan(p); }
 
 int msd_stream_buffers(msd_stream_plan *p, double **delta, double **tail, int64_t *n_tail, double **head,
                        int64_t *n_head, double **thresholds) {
     if (!p) return fail(MSD_ERR_INVALID, "msd_stream_buffers: null plan");
-    if (delta) *delta = p->d_x + p->n_tail;
-    if (tail) *tail = p->d_x;
+    if (delta) *delta = p->d_x.get() + p->n_tail;
+    if (tail) *tail = p->d_x.get();
     if (n_tail) *n_tail = p->n_tail;
-    if (head) *head = p->d_x + p->n_tail + p->n_local;
+    if (head) *head = p->d_x.get() + p->n_tail + p->n_local;
     if (n_head) *n_head = p->n_head;
-    if (thresholds) *thresholds = p->d_thr;
+    if (thresholds) *thresholds = p->d_thr.get();
     return MSD_OK;
 }
 
@@ -1379,13 +1348,13 @@ int msd_stream_chunk_sums(msd_stream_plan *p, int32_t use_mean, double mean, dou
     const int64_t x0 = p->frame0 - p->n_tail;
     const unsigned blocks = (unsigned)((nc + 3) / 4);
     if (use_mean)
-        hipLaunchKernelGGL(chunk_sums_kernel<true>, dim3(blocks), dim3(256), 0, p->ctx->stream, p->d_x, x0, c0, nc,
-                           p->n_total, mean, nullptr, p->d_chunks);
+        hipLaunchKernelGGL(chunk_sums_kernel<true>, dim3(blocks), dim3(256), 0, p->ctx->stream, p->d_x.get(), x0, c0, nc,
+                           p->n_total, mean, nullptr, p->d_chunks.get());
     else
-        hipLaunchKernelGGL(chunk_sums_kernel<false>, dim3(blocks), dim3(256), 0, p->ctx->stream, p->d_x, x0, c0, nc,
-                           p->n_total, 0.0, nullptr, p->d_chunks);
+        hipLaunchKernelGGL(chunk_sums_kernel<false>, dim3(blocks), dim3(256), 0, p->ctx->stream, p->d_x.get(), x0, c0, nc,
+                           p->n_total, 0.0, nullptr, p->d_chunks.get());
     MSD_HIP(hipGetLastError());
-    MSD_HIP(hipMemcpyAsync(pin_chunks(p), p->d_chunks, sizeof(double) * nc, hipMemcpyDeviceToHost, p->ctx->stream));
+    MSD_HIP(hipMemcpyAsync(pin_chunks(p), p->d_chunks.get(), sizeof(double) * nc, hipMemcpyDeviceToHost, p->ctx->stream));
     MSD_HIP(hipStreamSynchronize(p->ctx->stream));
     std::memcpy(sums, pin_chunks(p), sizeof(double) * nc);
     return MSD_OK;
@@ -1416,8 +1385,8 @@ int msd_stream_predicted(msd_stream_plan *p, double *fresh, double *eps) {
     if (p->n_local == 0) return MSD_OK;
     DeviceGuard g(p->ctx->device);
     hipStream_t st = p->ctx->stream;
-    if (fresh) MSD_HIP(hipMemcpyAsync(fresh, p->d_fresh, sizeof(double) * p->n_local, hipMemcpyDeviceToHost, st));
-    if (eps) MSD_HIP(hipMemcpyAsync(eps, p->d_eps, sizeof(double) * p->n_local, hipMemcpyDeviceToHost, st));
+    if (fresh) MSD_HIP(hipMemcpyAsync(fresh, p->d_fresh.get(), sizeof(double) * p->n_local, hipMemcpyDeviceToHost, st));
+    if (eps) MSD_HIP(hipMemcpyAsync(eps, p->d_eps.get(), sizeof(double) * p->n_local, hipMemcpyDeviceToHost, st));
     MSD_HIP(hipStreamSynchronize(st));
     return MSD_OK;
 }
@@ -1435,8 +1404,8 @@ int msd_stream_fresh(msd_stream_plan *p) {
     // decisions-only: every frame predicted (with its error bound), exact ones listed by the scan
     p->decide = !p->want_exact && P.W > 0 && !all;
     // need = 0 (1 with MSD_OPT_FRESH_ALL), done = 0, exact = 0 (decisions only): one launch
-    hipLaunchKernelGGL(fresh_clear_kernel, dim3(512), dim3(256), 0, st, p->d_need, p->ntiles,
-                       all ? 1 : 0, p->d_done, p->ntiles + 1, p->decide ? p->d_exact : nullptr,
+    hipLaunchKernelGGL(fresh_clear_kernel, dim3(512), dim3(256), 0, st, p->d_need.get(), p->ntiles,
+                       all ? 1 : 0, p->d_done.get(), p->ntiles + 1, p->decide ? p->d_exact.get() : nullptr,
                        p->n_local);
     // frames [0, jshort) have windows shorter than W: exact right away
     int64_t jshort = P.W - p->frame0;
@@ -1445,23 +1414,23 @@ int msd_stream_fresh(msd_stream_plan *p) {
     if (p->decide) jshort = 0;
     if (jshort > 0)
         hipLaunchKernelGGL(fresh_short_kernel, dim3((unsigned)std::min<int64_t>((jshort + 3) / 4, 4096)), dim3(256), 0,
-                           st, p->d_x, P, jshort, p->d_fresh);
+                           st, p->d_x.get(), P, jshort, p->d_fresh.get());
     if (jshort < p->n_local) {  // the predictor for full windows
         const int64_t nb = P.x_len / PB + 1;
-        hipLaunchKernelGGL(blocksum_kernel, dim3((unsigned)((nb + 3) / 4)), dim3(256), 0, st, p->d_x, P.x_len,
-                           nb, p->d_pre);
-        hipLaunchKernelGGL(blockscan_kernel, dim3(1), dim3(1024), 0, st, p->d_pre, nb);
+        hipLaunchKernelGGL(blocksum_kernel, dim3((unsigned)((nb + 3) / 4)), dim3(256), 0, st, p->d_x.get(), P.x_len,
+                           nb, p->d_pre.get());
+        hipLaunchKernelGGL(blockscan_kernel, dim3(1), dim3(1024), 0, st, p->d_pre.get(), nb);
         const int64_t m = p->n_local - jshort;
-        hipLaunchKernelGGL(approx_kernel, dim3((unsigned)((m + 255) / 256)), dim3(256), 0, st, p->d_x, p->d_pre, P,
-                           jshort, p->d_fresh, p->decide ? p->d_eps : nullptr);
+        hipLaunchKernelGGL(approx_kernel, dim3((unsigned)((m + 255) / 256)), dim3(256), 0, st, p->d_x.get(), p->d_pre.get(), P,
+                           jshort, p->d_fresh.get(), p->decide ? p->d_eps.get() : nullptr);
     }
     if (p->certify) {  // the thresholds' error bounds from the windows' delta error bounds
         const int64_t nb = P.x_len / PB + 1;
-        hipLaunchKernelGGL(blocksum_kernel, dim3((unsigned)((nb + 3) / 4)), dim3(256), 0, st, p->d_ed, P.x_len, nb,
-                           p->d_pre_e);
-        hipLaunchKernelGGL(blockscan_kernel, dim3(1), dim3(1024), 0, st, p->d_pre_e, nb);
-        hipLaunchKernelGGL(terr_kernel, dim3((unsigned)((p->n_local + 255) / 256)), dim3(256), 0, st, p->d_ed,
-                           p->d_pre_e, P, p->d_terr);
+        hipLaunchKernelGGL(blocksum_kernel, dim3((unsigned)((nb + 3) / 4)), dim3(256), 0, st, p->d_ed.get(), P.x_len, nb,
+                           p->d_pre_e.get());
+        hipLaunchKernelGGL(blockscan_kernel, dim3(1), dim3(1024), 0, st, p->d_pre_e.get(), nb);
+        hipLaunchKernelGGL(terr_kernel, dim3((unsigned)((p->n_local + 255) / 256)), dim3(256), 0, st, p->d_ed.get(),
+                           p->d_pre_e.get(), P, p->d_terr.get());
     }
     MSD_HIP(hipGetLastError());
     return MSD_OK;
@@ -1477,9 +1446,9 @@ int msd_stream_set_certify(msd_stream_plan *p, int32_t on) {
 
 int msd_stream_error_buffers(msd_stream_plan *p, double **ed, double **tail, double **head) {
     if (!p) return fail(MSD_ERR_INVALID, "msd_stream_error_buffers: null plan");
-    if (ed) *ed = p->d_ed + p->n_tail;
-    if (tail) *tail = p->d_ed;
-    if (head) *head = p->d_ed + p->n_tail + p->n_local;
+    if (ed) *ed = p->d_ed.get() + p->n_tail;
+    if (tail) *tail = p->d_ed.get();
+    if (head) *head = p->d_ed.get() + p->n_tail + p->n_local;
     return MSD_OK;
 }
 
@@ -1488,8 +1457,8 @@ static int64_t ed_sums_async(msd_stream_plan *p, int64_t x0, int64_t x1) {
     const int64_t nb = x1 > x0 ? (x1 - x0 + CHUNK - 1) / CHUNK : 0;
     hipStream_t st = p->ctx->stream;
     if (nb > 0)
-        hipLaunchKernelGGL(ed_sums_kernel, dim3((unsigned)nb), dim3(256), 0, st, p->d_ed, x0, x1, p->d_esum);
-    hipLaunchKernelGGL(ed_total_kernel, dim3(1), dim3(256), 0, st, p->d_esum, nb);
+        hipLaunchKernelGGL(ed_sums_kernel, dim3((unsigned)nb), dim3(256), 0, st, p->d_ed.get(), x0, x1, p->d_esum.get());
+    hipLaunchKernelGGL(ed_total_kernel, dim3(1), dim3(256), 0, st, p->d_esum.get(), nb);
     return nb;
 }
 
@@ -1499,7 +1468,7 @@ int msd_stream_ed_sums(msd_stream_plan *p, double *s1, double *s2) {
     const int64_t nb = ed_sums_async(p, p->n_tail, p->n_tail + p->n_local);
     MSD_HIP(hipGetLastError());
     double2 r;
-    MSD_HIP(hipMemcpyAsync(pin_chunks(p), p->d_esum + nb, sizeof(double2), hipMemcpyDeviceToHost, p->ctx->stream));
+    MSD_HIP(hipMemcpyAsync(pin_chunks(p), p->d_esum.get() + nb, sizeof(double2), hipMemcpyDeviceToHost, p->ctx->stream));
     MSD_HIP(hipStreamSynchronize(p->ctx->stream));
     std::memcpy(&r, pin_chunks(p), sizeof(r));
     *s1 = r.x;
@@ -1524,14 +1493,8 @@ int msd_stream_set_terr0(msd_stream_plan *p, double s1, double s2) {
 static int cert_staging(msd_stream_plan *p, double2 **sl, int32_t **cnt, longlong2 **u) {
     const size_t need =
         sizeof(double2) * p->nseg + sizeof(int32_t) * (p->nseg + 1) + sizeof(longlong2) * p->nseg * UCAP;
-    if (p->h_cert_bytes < need) {
-        if (p->h_cert) (void)hipHostFree(p->h_cert);
-        p->h_cert = nullptr;
-        p->h_cert_bytes = 0;
-        MSD_HIP(hipHostMalloc(&p->h_cert, need, hipHostMallocDefault));
-        p->h_cert_bytes = need;
-    }
-    *sl = static_cast<double2 *>(p->h_cert);
+    if (int rc = p->h_cert.grow(need, "stream certificate staging")) return rc;
+    *sl = static_cast<double2 *>(p->h_cert.get());
     *cnt = reinterpret_cast<int32_t *>(*sl + p->nseg);
     *u = reinterpret_cast<longlong2 *>(*cnt + p->nseg + (p->nseg & 1));
     return MSD_OK;
@@ -1544,8 +1507,8 @@ static int cert_enqueue(msd_stream_plan *p) {
     longlong2 *u;
     if (int rc = cert_staging(p, &sl, &cnt, &u)) return rc;
     hipStream_t st = p->ctx->stream;
-    MSD_HIP(hipMemcpyAsync(sl, p->d_slack, sizeof(double2) * p->nseg, hipMemcpyDeviceToHost, st));
-    MSD_HIP(hipMemcpyAsync(cnt, p->d_ucnt, sizeof(int32_t) * p->nseg, hipMemcpyDeviceToHost, st));
+    MSD_HIP(hipMemcpyAsync(sl, p->d_slack.get(), sizeof(double2) * p->nseg, hipMemcpyDeviceToHost, st));
+    MSD_HIP(hipMemcpyAsync(cnt, p->d_ucnt.get(), sizeof(int32_t) * p->nseg, hipMemcpyDeviceToHost, st));
     return MSD_OK;
 }
 
@@ -1581,7 +1544,7 @@ int msd_stream_certificate(msd_stream_plan *p, int64_t *uncertain, double *min_s
     }
     *uncertain = tot;
     if (tot == 0 || !frames || !srcs || cap <= 0) return MSD_OK;
-    MSD_HIP(hipMemcpyAsync(u, p->d_unc, sizeof(longlong2) * p->nseg * UCAP, hipMemcpyDeviceToHost, st));
+    MSD_HIP(hipMemcpyAsync(u, p->d_unc.get(), sizeof(longlong2) * p->nseg * UCAP, hipMemcpyDeviceToHost, st));
     MSD_HIP(hipStreamSynchronize(st));
     int64_t n = 0;
     for (int64_t q = 0; q < p->nseg && n < cap; ++q) {
@@ -1603,13 +1566,13 @@ int msd_stream_refine(msd_stream_plan *p, int32_t *computed) {
     hipStream_t st = p->ctx->stream;
     FreshParams P;
     fresh_params(p, P);
-    int32_t *count = p->d_done + p->ntiles;
+    int32_t *count = p->d_done.get() + p->ntiles;
     if (p->decide && p->listed == 0) return MSD_OK;  // the last scan listed nothing
     if (p->decide) {  // the frames the scan rounds listed
         {
             KernelTimer timer(p->ctx, K_FRESH);
-            hipLaunchKernelGGL(fresh_list_kernel, dim3(1024), dim3(256), 0, st, p->d_x, P, p->d_list, count,
-                               p->d_fresh, p->d_exact);
+            hipLaunchKernelGGL(fresh_list_kernel, dim3(1024), dim3(256), 0, st, p->d_x.get(), P, p->d_list.get(), count,
+                               p->d_fresh.get(), p->d_exact.get());
         }
         MSD_HIP(hipGetLastError());
         MSD_HIP(hipMemcpyAsync(&pin_hdr(p)->computed, count, sizeof(int32_t), hipMemcpyDeviceToHost, st));
@@ -1621,8 +1584,8 @@ int msd_stream_refine(msd_stream_plan *p, int32_t *computed) {
     MSD_HIP(hipMemsetAsync(count, 0, sizeof(int32_t), st));
     {
         KernelTimer timer(p->ctx, K_FRESH);
-        hipLaunchKernelGGL(fresh_kernel, dim3((unsigned)p->ntiles), dim3(FR_THREADS), 0, st, p->d_x, P, p->d_prog,
-                           p->d_fresh, p->d_need, p->d_done, count);
+        hipLaunchKernelGGL(fresh_kernel, dim3((unsigned)p->ntiles), dim3(FR_THREADS), 0, st, p->d_x.get(), P, p->d_prog.get(),
+                           p->d_fresh.get(), p->d_need.get(), p->d_done.get(), count);
     }
     MSD_HIP(hipGetLastError());
     MSD_HIP(hipMemcpyAsync(&pin_hdr(p)->computed, count, sizeof(int32_t), hipMemcpyDeviceToHost, st));
@@ -1648,7 +1611,7 @@ int msd_stream_scan(msd_stream_plan *p, double thr0, const msd_stream_state *ent
         SState e0;
         std::memcpy(&e0, entry, sizeof(SState));
         hipLaunchKernelGGL(scan_entry_kernel, dim3((unsigned)((p->nseg + 2 + 255) / 256)), dim3(256), 0, st, st_in(p),
-                           p->d_active, p->nseg, e0, thr0, p->terr0, scan_mode);
+                           p->d_active.get(), p->nseg, e0, thr0, p->terr0, scan_mode);
         MSD_HIP(hipGetLastError());
     }
     p->thr0 = thr0;
@@ -1664,9 +1627,9 @@ int msd_stream_scan(msd_stream_plan *p, double thr0, const msd_stream_state *ent
     P.write_thr = p->decide ? 0 : 1;  // decisions only: the thresholds buffer is not an output
     P.terr0 = p->terr0;
     CertOut cert{nullptr, nullptr, nullptr, nullptr, nullptr};
-    if (p->certify) cert = CertOut{p->d_ed + p->n_tail, p->d_terr, p->d_unc, p->d_ucnt, p->d_slack};
-    int32_t *changed = p->d_active + p->nseg;
-    int32_t *overflow = p->d_active + p->nseg + 1;
+    if (p->certify) cert = CertOut{p->d_ed.get() + p->n_tail, p->d_terr.get(), p->d_unc.get(), p->d_ucnt.get(), p->d_slack.get()};
+    int32_t *changed = p->d_active.get() + p->nseg;
+    int32_t *overflow = p->d_active.get() + p->nseg + 1;
     // rounds are enqueued three at a time (a round with no active segment costs two empty
     // launches); the host checks the last round's change count, so a typical fixed point
     // (2-3 rounds) costs one round trip
@@ -1676,22 +1639,22 @@ int msd_stream_scan(msd_stream_plan *p, double thr0, const msd_stream_state *ent
         for (int r = 0; r < R; ++r) {
             {
                 KernelTimer timer(p->ctx, K_SSCAN);
-                hipLaunchKernelGGL(scan_kernel, dim3((unsigned)p->nseg), dim3(64), 0, st, p->d_x + p->n_tail,
-                                   p->d_fresh, P, st_in(p), st_out(p), p->d_active, p->d_runs, p->d_nruns,
-                                   p->d_margin, p->d_thr, overflow, nullptr, p->d_eps, p->d_exact,
-                                   p->decide ? p->d_list : nullptr, p->d_done + p->ntiles, changed, cert);
+                hipLaunchKernelGGL(scan_kernel, dim3((unsigned)p->nseg), dim3(64), 0, st, p->d_x.get() + p->n_tail,
+                                   p->d_fresh.get(), P, st_in(p), st_out(p), p->d_active.get(), p->d_runs.get(), p->d_nruns.get(),
+                                   p->d_margin.get(), p->d_thr.get(), overflow, nullptr, p->d_eps.get(), p->d_exact.get(),
+                                   p->decide ? p->d_list.get() : nullptr, p->d_done.get() + p->ntiles, changed, cert);
             }
             MSD_HIP(hipGetLastError());
             ++nround;
             hipLaunchKernelGGL(propagate_kernel, dim3((unsigned)((p->nseg + 255) / 256)), dim3(256), 0, st, st_in(p),
-                               st_out(p), p->d_active, p->nseg, p->seg_len, p->frame0, P.F0, changed);
+                               st_out(p), p->d_active.get(), p->nseg, p->seg_len, p->frame0, P.F0, changed);
             MSD_HIP(hipGetLastError());
         }
         PinHdr *h = pin_hdr(p);
         MSD_HIP(hipMemcpyAsync(&h->changed, changed, 2 * sizeof(int32_t), hipMemcpyDeviceToHost, st));
         MSD_HIP(hipMemcpyAsync(&h->ex, st_out(p) + (p->nseg - 1), sizeof(SState), hipMemcpyDeviceToHost, st));
         if (p->decide)  // frames listed so far: a refine with none to compute needs no GPU round trip
-            MSD_HIP(hipMemcpyAsync(&h->listed, p->d_done + p->ntiles, sizeof(int32_t), hipMemcpyDeviceToHost, st));
+            MSD_HIP(hipMemcpyAsync(&h->listed, p->d_done.get() + p->ntiles, sizeof(int32_t), hipMemcpyDeviceToHost, st));
         MSD_HIP(hipStreamSynchronize(st));
         ex = h->ex;
         if (p->decide) p->listed = h->listed;
@@ -1706,15 +1669,15 @@ int msd_stream_scan(msd_stream_plan *p, double thr0, const msd_stream_state *ent
         // frames (near ties and triggers on predicted thresholds) in every round instead, appended at
         // the counter after d_done, which msd_stream_refine consumes and clears: a speculative
         // round lists a few frames more, each once, and no extra pass is needed
-        MSD_HIP(hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(p->d_active), 1, p->nseg, st));
+        MSD_HIP(hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(p->d_active.get()), 1, p->nseg, st));
         {
             KernelTimer timer(p->ctx, K_SSCAN);
-            hipLaunchKernelGGL(scan_kernel, dim3((unsigned)p->nseg), dim3(64), 0, st, p->d_x + p->n_tail, p->d_fresh, P,
-                               st_in(p), st_out(p), p->d_active, p->d_runs, p->d_nruns, p->d_margin, p->d_thr,
-                               overflow, p->d_need, nullptr, nullptr, nullptr, nullptr, nullptr, cert);
+            hipLaunchKernelGGL(scan_kernel, dim3((unsigned)p->nseg), dim3(64), 0, st, p->d_x.get() + p->n_tail, p->d_fresh.get(), P,
+                               st_in(p), st_out(p), p->d_active.get(), p->d_runs.get(), p->d_nruns.get(), p->d_margin.get(), p->d_thr.get(),
+                               overflow, p->d_need.get(), nullptr, nullptr, nullptr, nullptr, nullptr, cert);
         }
         MSD_HIP(hipGetLastError());
-        MSD_HIP(hipMemsetAsync(p->d_active, 0, sizeof(int32_t) * p->nseg, st));
+        MSD_HIP(hipMemsetAsync(p->d_active.get(), 0, sizeof(int32_t) * p->nseg, st));
     }
     p->scanned = true;
     // mode 1 / 2 scanned every segment: with certification on, every segment's entries are current;
@@ -1734,11 +1697,11 @@ int msd_stream_runs(msd_stream_plan *p, msd_det *runs, int64_t cap, int64_t *cou
     if (!p->scanned) return fail(MSD_ERR_INVALID, "msd_stream_runs: call msd_stream_scan first");
     DeviceGuard g(p->ctx->device);
     hipStream_t st = p->ctx->stream;
-    hipLaunchKernelGGL(runs_kernel, dim3(1), dim3(RK_T), 0, st, p->d_runs, p->d_nruns, p->nseg, p->cap, p->d_out,
-                       p->d_count, p->d_pos);
+    hipLaunchKernelGGL(runs_kernel, dim3(1), dim3(RK_T), 0, st, p->d_runs.get(), p->d_nruns.get(), p->nseg, p->cap, p->d_out.get(),
+                       p->d_count.get(), p->d_pos.get());
     MSD_HIP(hipGetLastError());
-    MSD_HIP(hipMemcpyAsync(&pin_hdr(p)->count, p->d_count, sizeof(int64_t), hipMemcpyDeviceToHost, st));
-    MSD_HIP(hipMemcpyAsync(pin_margin(p), p->d_margin, sizeof(double) * p->nseg, hipMemcpyDeviceToHost, st));
+    MSD_HIP(hipMemcpyAsync(&pin_hdr(p)->count, p->d_count.get(), sizeof(int64_t), hipMemcpyDeviceToHost, st));
+    MSD_HIP(hipMemcpyAsync(pin_margin(p), p->d_margin.get(), sizeof(double) * p->nseg, hipMemcpyDeviceToHost, st));
     MSD_HIP(hipStreamSynchronize(st));
     const int64_t n = pin_hdr(p)->count;
     *count = n;
@@ -1747,7 +1710,7 @@ int msd_stream_runs(msd_stream_plan *p, msd_det *runs, int64_t cap, int64_t *cou
     if (n > cap) return fail(MSD_ERR_CAPACITY, "msd_stream_runs: more runs than capacity");
     if (n > 0) {
         if (!runs) return fail(MSD_ERR_INVALID, "msd_stream_runs: null runs");
-        MSD_HIP(hipMemcpy(runs, p->d_out, sizeof(msd_det) * n, hipMemcpyDeviceToHost));
+        MSD_HIP(hipMemcpy(runs, p->d_out.get(), sizeof(msd_det) * n, hipMemcpyDeviceToHost));
     }
     return MSD_OK;
 }
@@ -1762,9 +1725,9 @@ int msd_stream_db(msd_stream_plan *p, msd_det *dets, int64_t n) {
     DeviceGuard g(p->ctx->device);
     hipStream_t st = p->ctx->stream;
     void *d = nullptr;
-    if (int rc = ctx_scratch(p->ctx, 3, sizeof(msd_det) * n, &d)) return rc;
+    if (int rc = ctx_scratch(p->ctx, SCRATCH_DETECTIONS, sizeof(msd_det) * n, &d)) return rc;
     MSD_HIP(hipMemcpyAsync(d, dets, sizeof(msd_det) * n, hipMemcpyHostToDevice, st));
-    hipLaunchKernelGGL(db_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, p->d_x, x0,
+    hipLaunchKernelGGL(db_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, p->d_x.get(), x0,
                        reinterpret_cast<msd_det *>(d), n);
     MSD_HIP(hipGetLastError());
     MSD_HIP(hipMemcpyAsync(dets, d, sizeof(msd_det) * n, hipMemcpyDeviceToHost, st));
@@ -1808,19 +1771,19 @@ int msd_stream_detect_local(msd_stream_plan *p, int32_t exact_thresholds, msd_de
         hipStream_t st = p->ctx->stream;
         const int64_t nc = (n + CHUNK - 1) / CHUNK;
         const unsigned blocks = (unsigned)((nc + 3) / 4);
-        double *stats = p->d_chunks + (n / CHUNK + 2);
-        hipLaunchKernelGGL(chunk_sums_kernel<false>, dim3(blocks), dim3(256), 0, st, p->d_x, (int64_t)0, (int64_t)0, nc,
-                           n, 0.0, nullptr, p->d_chunks);
-        hipLaunchKernelGGL(stream_stats_kernel<0>, dim3(1), dim3(256), 0, st, p->d_chunks, nc, n, p->cfg.k_std, stats);
-        hipLaunchKernelGGL(chunk_sums_kernel<true>, dim3(blocks), dim3(256), 0, st, p->d_x, (int64_t)0, (int64_t)0, nc,
-                           n, 0.0, stats, p->d_chunks);
-        hipLaunchKernelGGL(stream_stats_kernel<1>, dim3(1), dim3(256), 0, st, p->d_chunks, nc, n, p->cfg.k_std, stats);
+        double *stats = p->d_chunks.get() + (n / CHUNK + 2);
+        hipLaunchKernelGGL(chunk_sums_kernel<false>, dim3(blocks), dim3(256), 0, st, p->d_x.get(), (int64_t)0, (int64_t)0, nc,
+                           n, 0.0, nullptr, p->d_chunks.get());
+        hipLaunchKernelGGL(stream_stats_kernel<0>, dim3(1), dim3(256), 0, st, p->d_chunks.get(), nc, n, p->cfg.k_std, stats);
+        hipLaunchKernelGGL(chunk_sums_kernel<true>, dim3(blocks), dim3(256), 0, st, p->d_x.get(), (int64_t)0, (int64_t)0, nc,
+                           n, 0.0, stats, p->d_chunks.get());
+        hipLaunchKernelGGL(stream_stats_kernel<1>, dim3(1), dim3(256), 0, st, p->d_chunks.get(), nc, n, p->cfg.k_std, stats);
         int64_t nbe = 0;
         if (p->certify) nbe = ed_sums_async(p, 0, n);  // thr0's error bound from the whole stream's ed
         MSD_HIP(hipGetLastError());
         MSD_HIP(hipMemcpyAsync(pin_chunks(p), stats + 1, sizeof(double), hipMemcpyDeviceToHost, st));
         if (p->certify)
-            MSD_HIP(hipMemcpyAsync(pin_chunks(p) + 1, p->d_esum + nbe, sizeof(double2), hipMemcpyDeviceToHost, st));
+            MSD_HIP(hipMemcpyAsync(pin_chunks(p) + 1, p->d_esum.get() + nbe, sizeof(double2), hipMemcpyDeviceToHost, st));
         MSD_HIP(hipStreamSynchronize(st));
         thr0 = pin_chunks(p)[0];
         if (p->certify) p->terr0 = terr0_from(pin_chunks(p)[1], pin_chunks(p)[2], n, p->cfg.k_std);
@@ -1843,11 +1806,11 @@ int msd_stream_detect_local(msd_stream_plan *p, int32_t exact_thresholds, msd_de
     // runs of the shard, compacted on the device
     DeviceGuard g(p->ctx->device);
     hipStream_t st = p->ctx->stream;
-    hipLaunchKernelGGL(runs_kernel, dim3(1), dim3(RK_T), 0, st, p->d_runs, p->d_nruns, p->nseg, p->cap, p->d_out,
-                       p->d_count, p->d_pos);
+    hipLaunchKernelGGL(runs_kernel, dim3(1), dim3(RK_T), 0, st, p->d_runs.get(), p->d_nruns.get(), p->nseg, p->cap, p->d_out.get(),
+                       p->d_count.get(), p->d_pos.get());
     MSD_HIP(hipGetLastError());
-    MSD_HIP(hipMemcpyAsync(&pin_hdr(p)->count, p->d_count, sizeof(int64_t), hipMemcpyDeviceToHost, st));
-    MSD_HIP(hipMemcpyAsync(pin_margin(p), p->d_margin, sizeof(double) * p->nseg, hipMemcpyDeviceToHost, st));
+    MSD_HIP(hipMemcpyAsync(&pin_hdr(p)->count, p->d_count.get(), sizeof(int64_t), hipMemcpyDeviceToHost, st));
+    MSD_HIP(hipMemcpyAsync(pin_margin(p), p->d_margin.get(), sizeof(double) * p->nseg, hipMemcpyDeviceToHost, st));
     MSD_HIP(hipStreamSynchronize(st));
     const int64_t nr = pin_hdr(p)->count;
     for (int64_t i = 0; i < p->nseg; ++i) *margin = pin_margin(p)[i] < *margin ? pin_margin(p)[i] : *margin;
@@ -1855,18 +1818,18 @@ int msd_stream_detect_local(msd_stream_plan *p, int32_t exact_thresholds, msd_de
     if (nr > cap) return fail(MSD_ERR_CAPACITY, "msd_stream_detect_local: more runs than capacity");
     if (nr == 0) return MSD_OK;
     if (!out) return fail(MSD_ERR_INVALID, "msd_stream_detect_local: null out");
-    if (!adaptive) MSD_HIP(hipMemcpy(out + (nr - 1), p->d_out + (nr - 1), sizeof(msd_det), hipMemcpyDeviceToHost));
+    if (!adaptive) MSD_HIP(hipMemcpy(out + (nr - 1), p->d_out.get() + (nr - 1), sizeof(msd_det), hipMemcpyDeviceToHost));
     if (!adaptive && out[nr - 1].stop == n) {  // burst_stops gets len-1 (main.py:414-415)
         out[nr - 1].stop = n - 1;
         if (out[nr - 1].stop - out[nr - 1].start <= 0)
             return fail(MSD_ERR_ASSERT, "Detection duration must be greater than 0");  // main.py:437
-        MSD_HIP(hipMemcpyAsync(p->d_out + (nr - 1), out + (nr - 1), sizeof(msd_det), hipMemcpyHostToDevice, st));
+        MSD_HIP(hipMemcpyAsync(p->d_out.get() + (nr - 1), out + (nr - 1), sizeof(msd_det), hipMemcpyHostToDevice, st));
     }
     // np.mean dB of every run (main.py:422-423, :501-502) on the run buffer itself
-    hipLaunchKernelGGL(db_kernel, dim3((unsigned)((nr + 255) / 256)), dim3(256), 0, st, p->d_x, (int64_t)0, p->d_out,
+    hipLaunchKernelGGL(db_kernel, dim3((unsigned)((nr + 255) / 256)), dim3(256), 0, st, p->d_x.get(), (int64_t)0, p->d_out.get(),
                        nr);
     MSD_HIP(hipGetLastError());
-    MSD_HIP(hipMemcpyAsync(out, p->d_out, sizeof(msd_det) * nr, hipMemcpyDeviceToHost, st));
+    MSD_HIP(hipMemcpyAsync(out, p->d_out.get(), sizeof(msd_det) * nr, hipMemcpyDeviceToHost, st));
     // certifying: the certificate's counts and slacks ride on the same sync
     if (p->certify && p->cert_valid) {
         if (int rc2 = cert_enqueue(p)) return rc2;

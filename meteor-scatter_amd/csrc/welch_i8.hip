@@ -555,9 +555,9 @@ int welch_i8_build(msd_welch_plan *p, const double *window) {
         }
     }
     const size_t nb_frag = frag.size(), nb_dbl = sizeof(double) * dbl.size();
-    hipError_t e = hipMalloc(&p->d_i8, nb_frag + nb_dbl);
-    char *base = static_cast<char *>(p->d_i8);
-    if (e == hipSuccess) e = hipMemcpy(base, frag.data(), nb_frag, hipMemcpyHostToDevice);
+    if (int rc = p->d_i8.alloc(nb_frag + nb_dbl, "welch plan: int8 tables")) return rc;
+    char *base = p->d_i8.get();
+    hipError_t e = hipMemcpy(base, frag.data(), nb_frag, hipMemcpyHostToDevice);
     if (e == hipSuccess) e = hipMemcpy(base + nb_frag, dbl.data(), nb_dbl, hipMemcpyHostToDevice);
     if (e != hipSuccess) return hip_fail(e, "welch plan: int8 tables");
     p->i8_nct = nct;
@@ -575,7 +575,7 @@ int launch_welch_i8(msd_welch_plan *p, const int16_t *x, const int64_t *off, con
     if (!psd) {
         const size_t bytes = sizeof(double) * (size_t)nfiles * (size_t)ld * (size_t)p->nslots;
         void *s = nullptr;
-        if (int rc = ctx_scratch(p->ctx, 5, bytes, &s)) return rc;
+        if (int rc = ctx_scratch(p->ctx, SCRATCH_WELCH_PSD, bytes, &s)) return rc;
         psd = static_cast<double *>(s);
     }
     WelchI8Args A{};
@@ -608,9 +608,8 @@ int launch_welch_i8(msd_welch_plan *p, const int16_t *x, const int64_t *off, con
     A.pairs = p->i8_pairs && !(form & 1);
     A.rnseg = 1.0 / (double)A.nseg;
     const size_t lds = (size_t)A.cg * per_ct + scratch;
-    const v4i *frag = static_cast<const v4i *>(p->d_i8);
-    const double *dbl = reinterpret_cast<const double *>(static_cast<const char *>(p->d_i8) +
-                                                         (size_t)nct * WI_ND * KS * 64 * 16);
+    const v4i *frag = reinterpret_cast<const v4i *>(p->d_i8.get());
+    const double *dbl = reinterpret_cast<const double *>(p->d_i8.get() + (size_t)nct * WI_ND * KS * 64 * 16);
     const unsigned grid = (unsigned)(8 * A.ngroups * A.reps);
     hipStream_t st = p->ctx->stream;
     KernelTimer timer(p->ctx, K_WELCH);
