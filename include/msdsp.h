@@ -123,7 +123,8 @@ int msd_set_option(msd_ctx *ctx, int option, int value);
  * kernel id: 0 = STFT power, 1 = block delta, 2 = detector stats, 3 = detector scan,
  * 4 = Welch band powers, 5 = live detector, 6 = complex (I/Q) STFT, 7 = I/Q band delta,
  * 8 = stream fresh thresholds, 9 = stream scan, 10 = float64 delta (msd_iq_delta64_dev),
- * 11 = the I/Q STFT's post-FFT detrend of bins 0, +-1 (its separate fix-up kernels). */
+ * 11 = the I/Q STFT's post-FFT detrend of bins 0, +-1 (its separate fix-up kernels),
+ * 12 = Welch spectrum (msd_welch_spectrum*). */
 int msd_timing_enable(msd_ctx *ctx, int enable);
 /* which kernels get events while timing is on: bit k = kernel id k (default all); a timed
  * region that times only its roofline kernel carries no events around the others */
@@ -512,6 +513,19 @@ int msd_welch_bands(msd_welch_plan *plan, const void *x, int dtype, int64_t n, d
 /* single signal, host buffers: the per-block PSD of the band bins, psd [nb][nslots] (one band
  * 0..nfft/2 and block_size = n gives scipy.signal.welch(x, fs, ...)'s whole PSD) */
 int msd_welch_psd(msd_welch_plan *plan, const void *x, int dtype, int64_t n, double *psd, int64_t *blocks);
+/* The whole one-sided Welch PSD of every block by a pruned float64 FFT (csrc/welch_fft.hip) instead of
+ * one Goertzel recurrence per bin: scipy.signal.welch(block, fs, nperseg=, noverlap=, nfft=) for all
+ * K = nfft/2 + 1 bins, and db_mean = np.mean(10*log10(row)) per block (log10(0) = -inf, as numpy's).
+ * nfft a power of two in [16, 16384], any nperseg <= nfft, any noverlap < nperseg; anything else returns
+ * MSD_ERR_UNSUPPORTED with nothing launched.  A block's row does not depend on the launch, the file
+ * slot or the position in the batch that computed it.
+ * whole one-sided Welch PSD of every block: psd[(f*ld + b)*K + k], K = nfft/2+1; db_mean[f*ld + b]
+ * (may be NULL).  The plan's bands are ignored.  Entries at b >= blocks of file f are not written. */
+int msd_welch_spectrum_dev(msd_welch_plan *plan, const void *x, int dtype, const int64_t *off, const int64_t *len,
+                           int64_t nfiles, int64_t max_blocks, double *psd, int64_t ld, double *db_mean);
+/* single signal, host buffers: psd [nb][K], db_mean (may be NULL) [nb] */
+int msd_welch_spectrum(msd_welch_plan *plan, const void *x, int dtype, int64_t n, double *psd, double *db_mean,
+                       int64_t *blocks);
 
 /* The integer coefficients the exact int8-MFMA band kernels are built from (host only: no context,
  * no GPU), so that a test can restate their arithmetic in integers.  kind 0: the block plan's

@@ -10,6 +10,7 @@
 
 #include "../../include/msdsp.h"
 #include "dev_mem.h"
+#include "welch_fft_plan.h"
 
 namespace msd {
 
@@ -27,7 +28,7 @@ int ensure_dyn_lds(const void *kernel, int bytes);
     } while (0)
 
 enum KernelId { K_STFT = 0, K_BLOCK = 1, K_DSTAT = 2, K_DSCAN = 3, K_WELCH = 4, K_LIVE = 5, K_CSTFT = 6, K_IQDELTA = 7, K_FRESH = 8, K_SSCAN = 9,
-               K_REFINE = 10, K_CSTFT_DC = 11, K_COUNT = 12 };
+               K_REFINE = 10, K_CSTFT_DC = 11, K_WSPEC = 12, K_COUNT = 13 };
 
 struct EventPair {
     hipEvent_t a, b;
@@ -182,6 +183,10 @@ struct msd_welch_plan {
     msd::DevBuf<char> d_i8;
     int i8_nct = 0;
     bool i8_pairs = false;  // the accumulators' digit sums fit int32 pairs (welch_i8_build)
+    // the whole-band row (welch_fft.hip), built by the first call that needs it (welch_spectrum_prepare)
+    msd::wfft::Plan fft{};
+    int fft_state = 0;             // 0 not built, 1 built, -1 a shape the transform does not take
+    msd::DevBuf<double2> d_roots;  // [nfft] W_nfft^j
 };
 
 namespace msd {
@@ -350,6 +355,11 @@ bool welch_i8_shape(const msd_welch_cfg &c, int nseg, int nslots, const double *
 int welch_i8_build(msd_welch_plan *p, const double *window);
 int launch_welch_i8(msd_welch_plan *p, const int16_t *x, const int64_t *off, const int64_t *len, int64_t nfiles,
                     int64_t max_blocks, double *band_db, int64_t ld, double *psd);
+// the whole-band Welch row of every block (welch_fft.hip): psd[(f*ld + b)*K + k], db_mean[f*ld + b] (may be
+// null); prepare builds the plan's transform tables (a blocking upload, once)
+int welch_spectrum_prepare(msd_welch_plan *p);
+int launch_welch_spectrum(msd_welch_plan *p, const void *x, int dtype, const int64_t *off, const int64_t *len,
+                          int64_t nfiles, int64_t max_blocks, double *psd, int64_t ld, double *db_mean);
 int block_i8_build(msd_block_plan *p, const double *window, const int *bins, int nbins);
 int launch_block_i8(msd_block_plan *p, const int16_t *x, const int64_t *off, const int64_t *len, int64_t nfiles,
                     int64_t max_blocks);

@@ -36,6 +36,7 @@ DTYPE_CODES = {
 
 K_STFT, K_BLOCK, K_DSTAT, K_DSCAN, K_WELCH, K_LIVE, K_CSTFT = 0, 1, 2, 3, 4, 5, 6
 K_IQDELTA, K_FRESH, K_SSCAN, K_REFINE, K_CSTFT_DC = 7, 8, 9, 10, 11
+K_WSPEC = 12  # Welch spectrum (whole-band rows)
 OPT_GENERIC_STFT = 1
 OPT_FRESH_ALL = 2
 OPT_REFINE_GOERTZEL = 3
@@ -225,6 +226,8 @@ _SIGS = [
     ("msd_welch_bands_dev", C.c_int, [_P, _P, C.c_int, _P, _P, C.c_int64, C.c_int64, _P, C.c_int64, _P]),
     ("msd_welch_bands", C.c_int, [_P, _P, C.c_int, C.c_int64, _P, C.POINTER(C.c_int64)]),
     ("msd_welch_psd", C.c_int, [_P, _P, C.c_int, C.c_int64, _P, C.POINTER(C.c_int64)]),
+    ("msd_welch_spectrum_dev", C.c_int, [_P, _P, C.c_int, _P, _P, C.c_int64, C.c_int64, _P, C.c_int64, _P]),
+    ("msd_welch_spectrum", C.c_int, [_P, _P, C.c_int, C.c_int64, _P, _P, C.POINTER(C.c_int64)]),
     ("msd_i8_coeffs", C.c_int, [C.c_int, _P, C.c_int, C.c_int, C.c_int, C.c_int, _P]),
     ("msd_live_detect_dev", C.c_int,
      [_P, _P, _P, C.c_int64, C.c_int64, C.POINTER(MsdLiveCfg), _P, C.c_int64, _P, _P, _P, _P]),
@@ -628,6 +631,24 @@ class WelchPlan:
         check(self.ctx.lib.msd_welch_psd(self.h, ptr(x), dtype_code(x.dtype), int(x.shape[0]), ptr(out),
                                          C.byref(got)))
         return out
+
+    def spectrum(self, x: np.ndarray):
+        """(psd [nb][nfft/2 + 1], db_mean [nb]): every block's whole Welch row by the pruned FFT and
+        np.mean(10 log10(row)) (host buffers)"""
+        x = np.ascontiguousarray(x)
+        nb = self.blocks(x.shape[0])
+        out = np.empty((nb, int(self.cfg.nfft) // 2 + 1), np.float64)
+        db = np.empty(nb, np.float64)
+        got = C.c_int64(0)
+        check(self.ctx.lib.msd_welch_spectrum(self.h, ptr(x), dtype_code(x.dtype), int(x.shape[0]), ptr(out), ptr(db),
+                                              C.byref(got)))
+        return out, db
+
+    def spectrum_dev(self, x: DeviceBuffer, dtype, off: DeviceBuffer, length: DeviceBuffer, nfiles: int,
+                     max_blocks: int, psd: DeviceBuffer, ld: int, db_mean: DeviceBuffer | None = None):
+        check(self.ctx.lib.msd_welch_spectrum_dev(self.h, x.ptr, dtype_code(dtype), off.ptr, length.ptr, int(nfiles),
+                                                  int(max_blocks), psd.ptr, int(ld),
+                                                  db_mean.ptr if db_mean else None))
 
     def run_dev(self, x: DeviceBuffer, dtype, off: DeviceBuffer, length: DeviceBuffer, nfiles: int,
                 max_blocks: int, band_db: DeviceBuffer, ld: int, psd: DeviceBuffer | None = None):

@@ -10,7 +10,8 @@ full rows of the initialisation blocks that set its colour range).  The live UI 
 (``enable_ui_plots``, an interactive matplotlib window) is not part of the drop-in: asking for
 it raises ``NotImplementedError``.
 
-Lower-level pieces: ``welch_band_db`` (band dB rows of one signal), ``live_detect`` (the
+Lower-level pieces: ``welch_band_db`` (band dB rows of one signal), ``welch_spectrum`` (every block's
+whole-band PSD row and its dB mean, by a pruned FFT), ``live_detect`` (the
 state machine over band dB rows), ``LiveBatch`` (many recordings resident in HBM),
 ``LiveSession`` (the detector fed in chunks as the audio arrives, state kept on the GPU).
 """
@@ -189,6 +190,18 @@ def welch_band_db(x: np.ndarray, fs, config_detection: ConfigDetection, sample_s
     plan = _lib.WelchPlan(context(device), c, win)
     try:
         return plan.run(np.ascontiguousarray(x))
+    finally:
+        plan.close()
+
+
+def welch_spectrum(x: np.ndarray, fs, config_detection: ConfigDetection, sample_scale: float = 1.0, device: int = 0):
+    """Per-block whole-band Welch PSD by the pruned FFT (csrc/welch_fft.hip): (psd [nb][n_fft/2 + 1],
+    db_mean [nb]) -- processor.py:206's ``block_psd`` of every block and :448's
+    ``np.mean(10 * np.log10(block_psd))``, float64."""
+    c, win = welch_cfg(fs, config_detection, sample_scale)
+    plan = _lib.WelchPlan(context(device), c, win)
+    try:
+        return plan.spectrum(np.ascontiguousarray(x))
     finally:
         plan.close()
 
