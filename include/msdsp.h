@@ -124,7 +124,7 @@ int msd_set_option(msd_ctx *ctx, int option, int value);
  * 4 = Welch band powers, 5 = live detector, 6 = complex (I/Q) STFT, 7 = I/Q band delta,
  * 8 = stream fresh thresholds, 9 = stream scan, 10 = float64 delta (msd_iq_delta64_dev),
  * 11 = the I/Q STFT's post-FFT detrend of bins 0, +-1 (its separate fix-up kernels),
- * 12 = Welch spectrum (msd_welch_spectrum*). */
+ * 12 = Welch spectrum (msd_welch_spectrum*), 13 = DDC (the down-converter's tile kernel, msd_ddc_*). */
 int msd_timing_enable(msd_ctx *ctx, int enable);
 /* which kernels get events while timing is on: bit k = kernel id k (default all); a timed
  * region that times only its roofline kernel carries no events around the others */
@@ -683,6 +683,75 @@ int msd_live_session_history(msd_live_session *s, int64_t stream, double *out, i
 /* stream >= 0: that stream, -1: all, back to Init at block 0 with empty history and remainder
  * and status 0.  Enqueued on the context's stream. */
 int msd_live_session_reset(msd_live_session *s, int64_t stream);
+
+/* ------------------------------ decimating down-converter: the receiver's last stage
+ * The phase-2 detector above takes 4 kHz audio in which the carrier sits at 1 kHz (the reference
+ * asserts file_sample_rate == 4000 and leaves the conversion to gqrx / HDSDR).  This makes that audio
+ * from what is recorded: 48 kHz audio (MSD_DDC_REAL: low-pass and decimate) or wide-band I/Q
+ * (MSD_DDC_SSB: tune, low-pass, decimate and take the single-sideband audio, a Weaver demodulator).
+ *
+ * Contract.  x[n]: one stream's samples, n the global sample index (int64, from 0); h[0 .. ntaps-1]: real
+ * float64 taps, ntaps odd, c = (ntaps-1)/2; D = decim.  Samples outside what a call or a stream has seen
+ * count as zero.
+ *   REAL (MSD_I16 or MSD_F32):  v[m] = sum_{k=0}^{ntaps-1} h[k] x[m D + c - k],  y[m] = gain v[m].
+ *   SSB (MSD_CI16 or MSD_CF32, interleaved I, Q):  z[n] = x[n] e^{-2 pi i r(n)/q},  r(n) = (n p) mod q exactly
+ *   in integers,  p/q = shift_num/shift_den in lowest terms (cycles per input sample);  v[m] as above over z;
+ *   y[m] = gain Re(i^m v[m]).  With shift = (f_signal - f_tone + fs_out/4)/fs_in and a low-pass below
+ *   fs_out/4 a carrier at f_signal comes out as a real tone at f_tone and the other sideband is rejected.
+ * Outputs.  A batch row holding samples [pos0, pos0+N) emits every m with pos0 <= m D < pos0+N:
+ * ceil((pos0+N)/D) - ceil(pos0/D) of them.  A stream that has received N_tot samples has emitted every m
+ * with m D + c < N_tot; msd_ddc_flush emits the rest, m D < N_tot, with zeros for the samples to come; a
+ * flushed stream must be reset before it is pushed again.  msd_ddc_reset(plan, stream, pos0) clears the
+ * history and sets the stream's position (stream -1: all), so a stream may start anywhere.
+ * Output dtype: MSD_F64, or MSD_I16 = rint(y) (ties to even) saturated to [-32768, 32767].
+ * Arithmetic: float64, no contraction but the kernel's explicit FMAs.  The summation order of an output
+ * is a function of (ntaps, D) alone (csrc/ddc_plan.h), never of tile, grid, chunking or entry point:
+ * pushes of any lengths followed by flush equal one msd_ddc_run over the concatenation bit for bit, and a
+ * row with c samples of halo on each side equals the whole stream on its interior outputs bit for bit.
+ * Error: |y - y_exact| <= chain u gain S_m, u = 2^-53, S_m = sum_k |h_k| |x_{m D + c - k}|, chain =
+ * msd_ddc_chain (counted from the kernel's code, csrc/ddc_plan.h).
+ * Limits: 1 <= decim <= 1024; ntaps odd in 1 .. 4095; reduced 1 <= q <= 2^24, 0 <= p < q; positions up to
+ * 2^62.  REAL with p != 0 and sizes outside the limits: MSD_ERR_UNSUPPORTED; an even ntaps, a dtype that
+ * does not fit the mode, a bad out_dtype: MSD_ERR_INVALID.
+ * Streams: nstreams >= 0 independent streams whose state lives in the plan on the device: the position
+ * and the last ntaps-1 raw samples (raw, not mixed: the phase comes from the global index).  A stream
+ * keeps the dtype of its first push until it is reset.  max_push: the most samples one push brings per
+ * stream (longer device pushes are cut to it).
+ * _dev calls only enqueue on the context's stream.  off / len / pos0: device int64 arrays (samples of
+ * dtype; a complex sample is one sample).  y: rows of ld_out outputs of the plan's out_dtype; out_len:
+ * device int64, the row's full count.  Only the first ld_out outputs of a row are written and nothing
+ * past a row's count is touched; msd_ddc_push_dev needs ld_out >= ceil(max_push / D).
+ * The host forms return MSD_ERR_CAPACITY (with *out_len set, nothing copied) when cap is too small. */
+#define MSD_DDC_REAL 0
+#define MSD_DDC_SSB 1
+typedef struct {
+    int32_t mode, decim, ntaps, out_dtype;
+    int64_t shift_num, shift_den;
+    double gain;
+} msd_ddc_cfg;
+typedef struct msd_ddc_plan msd_ddc_plan;
+int msd_ddc_plan_create(msd_ctx *ctx, const msd_ddc_cfg *cfg, const double *taps, int64_t nstreams, int64_t max_push,
+                        msd_ddc_plan **out);
+void msd_ddc_plan_destroy(msd_ddc_plan *plan);
+/* host only, no context: the first output index and the output count of a row [pos0, pos0 + n) */
+int msd_ddc_out_len(const msd_ddc_cfg *cfg, int64_t pos0, int64_t n, int64_t *m0, int64_t *count);
+/* host only, no context: the rounding chain of the bound above */
+int msd_ddc_chain(const msd_ddc_cfg *cfg, double *chain);
+/* independent rows: row r holds samples [pos0[r], pos0[r] + len[r]) at x[off[r] ..] */
+int msd_ddc_run_dev(msd_ddc_plan *plan, const void *x, int dtype, const int64_t *off, const int64_t *len,
+                    const int64_t *pos0, int64_t nrows, void *y, int64_t ld_out, int64_t *out_len);
+/* one row, host buffers */
+int msd_ddc_run(msd_ddc_plan *plan, const void *x, int dtype, int64_t n, int64_t pos0, void *y, int64_t cap,
+                int64_t *out_len);
+/* all nstreams: stream f's new samples are x[off[f] .. off[f] + min(len[f], max_push)) */
+int msd_ddc_push_dev(msd_ddc_plan *plan, const void *x, int dtype, const int64_t *off, const int64_t *len, void *y,
+                     int64_t ld_out, int64_t *out_len);
+/* one stream, host buffers, n <= max_push */
+int msd_ddc_push(msd_ddc_plan *plan, int64_t stream, const void *x, int dtype, int64_t n, void *y, int64_t cap,
+                 int64_t *out_len);
+/* one stream, host buffers: at most ceil(c / D) + 1 outputs */
+int msd_ddc_flush(msd_ddc_plan *plan, int64_t stream, void *y, int64_t cap, int64_t *out_len);
+int msd_ddc_reset(msd_ddc_plan *plan, int64_t stream, int64_t pos0);
 
 /* ------------------------------------------- a1 / §8(f)1: WAV ingest and uploads
  * scipy.io.wavfile.read semantics for the reference's files (dsp/src/main.py:249; the rules in
