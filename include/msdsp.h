@@ -465,6 +465,23 @@ int msd_iq_delta64_sums_dev(msd_ctx *ctx, const void *x, int32_t dtype, int64_t 
 #define MSD_REFINE_INT8_MFMA 3
 int msd_iq_delta64_path(int32_t nperseg, int64_t hop, double fs, int32_t band_lo, int32_t band_hi, int32_t noise_lo,
                         int32_t noise_hi, int32_t dtype);
+/* The rounding chain behind ed for a geometry, in its three parts, in units of u = 2^-53 (host only,
+ * no context): own = the block step the geometry takes (MSD_REFINE_INT8_MFMA: the three constants
+ * below, 119; MSD_REFINE_GOERTZEL_ROWS: 3 L Gmax + 12 with L = D / 16 samples per lane and Gmax =
+ * min(max over the needed bins of 1 / |sin theta|, L); MSD_REFINE_DIRECT: D + 4), combine = the frame
+ * step ((R + 4) for the R block rotations and sums, 8 for the mean, the Hann taps and |Y|^2),
+ * reference = the float64 reference's own chain (4 log2 N + 11).  frame_kernel's bound uses their sum
+ * (own + (combine + reference), all integers when nperseg is a power of two).  The function honours no
+ * context: goertzel != 0 gives the figures a context with MSD_OPT_REFINE_GOERTZEL set runs int16 input
+ * with (the Goertzel rows instead of the int8 step).  Any of the three pointers may be NULL, not all.
+ * The int8 step's own chain is the twiddles' quantisation sqrt 2 * 2^-47 (1 + 2^-16) per unit |x| (91),
+ * the six-digit Horner sum (6) and the four sub-block products summed with rounded twiddles (22). */
+#define MSD_REFINE_I8_CHAIN_QUANT 91.0
+#define MSD_REFINE_I8_CHAIN_HORNER 6.0
+#define MSD_REFINE_I8_CHAIN_SUBBLOCK 22.0
+int msd_iq_delta64_chain(int32_t nperseg, int64_t hop, double fs, int32_t band_lo, int32_t band_hi, int32_t noise_lo,
+                         int32_t noise_hi, int32_t dtype, int32_t goertzel, double *own, double *combine,
+                         double *reference);
 
 /* ------------------------------------------- a10: legacy spectrogram noise floor
  * prime_detection.py:65-91: band_power = np.sum(Pxx[noise_band]) sums the spectrogram over
@@ -531,7 +548,11 @@ int msd_welch_spectrum(msd_welch_plan *plan, const void *x, int dtype, int64_t n
  * no GPU), so that a test can restate their arithmetic in integers.  kind 0: the block plan's
  * T_n = round(w_n cos(2 pi k n / nfft) 2^54) (part 0) or round(-w_n sin(...) 2^54) (part 1);
  * kind 1: the Welch plan's T_n ~ (w_n e^{-2 pi i k n / nfft} - W_k / L) 2^53, real (part 0) or
- * imaginary part, rounded so that sum_n T_n = 0.  window: L float64 in [-1, 1]; T: L values. */
+ * imaginary part, rounded so that sum_n T_n = 0.  window: L float64 in [-1, 1]; T: L values.
+ * kind 2: the refinement step's (msd_iq_delta64_dev on MSD_REFINE_INT8_MFMA) T_n = round(cos(2 pi k n /
+ * nfft) 2^46) (part 0) or round(sin(...) 2^46) (part 1) for 0 <= k < nfft and n < L <= 1024; the window
+ * is ignored and may be NULL.  The kernel multiplies sample n of a 256-sample sub-block by T_n (the
+ * imaginary component by -T^s_n), n < 256, and combines the sub-blocks in float64. */
 int msd_i8_coeffs(int kind, const double *window, int L, int nfft, int k, int part, int64_t *T);
 
 /* --------------------------------------------- a9: live detector state machine

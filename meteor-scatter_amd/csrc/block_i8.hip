@@ -278,6 +278,13 @@ int launch_block_i8(msd_block_plan *p, const int16_t *x, const int64_t *off, con
 // needs to restate their arithmetic exactly
 extern "C" int msd_i8_coeffs(int kind, const double *window, int L, int nfft, int k, int part, int64_t *T) {
     using namespace msd;
+    if (kind == 2) {  // the refinement step's twiddle integers (refine_i8.hip): no window
+        if (!T) return fail(MSD_ERR_INVALID, "msd_i8_coeffs: null");
+        if ((part != 0 && part != 1) || L < 1 || L > 1024 || nfft < 1 || k < 0 || k >= nfft)
+            return fail(MSD_ERR_INVALID, "msd_i8_coeffs: kind 2 needs part in {0, 1}, 1 <= L <= 1024, 0 <= k < nfft");
+        refine_i8_coeffs(L, nfft, k, part, T);
+        return MSD_OK;
+    }
     if (!window || !T) return fail(MSD_ERR_INVALID, "msd_i8_coeffs: null");
     if ((kind != 0 && kind != 1) || (part != 0 && part != 1) || L < 1 || nfft < 1 || k < 0 || k > nfft / 2)
         return fail(MSD_ERR_INVALID, "msd_i8_coeffs: need kind, part in {0, 1}, L, nfft >= 1, 0 <= k <= nfft / 2");

@@ -497,6 +497,36 @@ bool check_coeffs(int L, int nfft, int k, int part, std::string &why) {
     return true;
 }
 
+// refine_i8_coeffs (refine_i8.hip's table builder and msd_i8_coeffs kind 2 call it): every T in six
+// balanced digits, |T| <= 2^46, within 1/2 of the long-double value times 2^46, and exactly 2^46 (cos) and 0
+// (sin) at n = 0
+bool check_refine_coeffs(int nfft, int64_t k, std::string &why) {
+    const int L = 1024;
+    const std::string at = "refine_i8_coeffs nfft " + std::to_string(nfft) + " bin " + std::to_string(k);
+    for (int part = 0; part < 2; ++part) {
+        std::vector<int64_t> T(L);
+        msd::refine_i8_coeffs(L, nfft, k, part, T.data());
+        if (T[0] != (part ? 0 : int64_t(1) << 46)) {
+            why = at + ": n = 0 is not 2^46 / 0";
+            return false;
+        }
+        for (int n = 0; n < L; ++n) {
+            int8_t d[6];
+            if (!msd::balanced_digits<6>(T[n], d) || T[n] > (int64_t(1) << 46) || T[n] < -(int64_t(1) << 46)) {
+                why = at + ": a coefficient beyond six digits or 2^46 at n " + std::to_string(n);
+                return false;
+            }
+            long double c, sn;
+            msd::unit_root_ld(k * n, nfft, c, sn);
+            if (!(fabsl((long double)T[n] - (part ? sn : c) * 0x1p46L) <= 0.5L)) {
+                why = at + ": a coefficient off its value at n " + std::to_string(n);
+                return false;
+            }
+        }
+    }
+    return true;
+}
+
 int cmd_i8(uint64_t seed, int64_t iters) {
     std::string why;
     auto both = [&](int64_t T) { return check_digits<6>(T, why) && check_digits<7>(T, why); };
@@ -539,6 +569,15 @@ int cmd_i8(uint64_t seed, int64_t iters) {
                         std::printf("bad %s\n", why.c_str());
                         return 1;
                     }
+    for (int nfft = 1024; nfft <= 8192; nfft += 1024) {
+        std::vector<int64_t> ks = {2, nfft / 4, nfft / 2 - 1, nfft - 2};
+        for (int r = 0; r < 4; ++r) ks.push_back((int64_t)(g() % (uint64_t)nfft));
+        for (int64_t k : ks)
+            if (!check_refine_coeffs(nfft, k, why)) {
+                std::printf("bad %s\n", why.c_str());
+                return 1;
+            }
+    }
     // frag_sample: (g, j) onto the 64 samples of each K step, one to one
     for (int ks = 0; ks < 16; ++ks) {
         bool seen[64] = {};

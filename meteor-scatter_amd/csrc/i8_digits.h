@@ -129,6 +129,19 @@ inline bool welch_i8_coeffs(const double *window, int L, int nfft, int64_t k, in
     return true;
 }
 
+// refine_i8.hip's integers of bin k (0 <= k < nfft): T_n = round(cos(2 pi k n / nfft) 2^46) (part 0) or
+// round(sin(...) 2^46) (part 1), n < L, from the long-double unit root whose argument was reduced
+// exactly (unit_root_ld): |T_n 2^-46 - w_n| <= 2^-47 (1 + 2^-16), |T_n| <= 2^46 (six balanced digits).
+// The kernel's columns take T^c, T^s and -T^s (re = I C + Q S, im = Q C - I S) at n < 256, the
+// sample's place in its sub-block.
+inline void refine_i8_coeffs(int L, int nfft, int64_t k, int part, int64_t *T) {
+    for (int n = 0; n < L; ++n) {
+        long double c, s;
+        unit_root_ld(k * n, nfft, c, s);
+        T[n] = (int64_t)llroundl(ldexpl(part ? s : c, 46));
+    }
+}
+
 // the sample of a K dimension that byte j (< 16) of lane group g's (< 4) fragment of K step ks holds:
 // the A fragments' load order, which the B fragments' builders follow
 constexpr int frag_sample(int ks, int g, int j) { return 64 * ks + (j < 8 ? 8 * g + j : 32 + 8 * g + (j - 8)); }

@@ -334,6 +334,23 @@ int msd_iq_delta64_path(int32_t nperseg, int64_t hop, double fs, int32_t band_lo
     return P.G.rows ? MSD_REFINE_GOERTZEL_ROWS : MSD_REFINE_DIRECT;
 }
 
+// the parts of the chain frame_kernel is given (GF.chain below): own + (combine + reference)
+int msd_iq_delta64_chain(int32_t nperseg, int64_t hop, double fs, int32_t band_lo, int32_t band_hi, int32_t noise_lo,
+                         int32_t noise_hi, int32_t dtype, int32_t goertzel, double *own, double *combine,
+                         double *reference) {
+    if (!own && !combine && !reference) return fail(MSD_ERR_INVALID, "msd_iq_delta64_chain: null");
+    if (dtype != MSD_CI16 && dtype != MSD_CF32) return fail(MSD_ERR_UNSUPPORTED, "msd_iq_delta64_chain: CI16 or CF32");
+    RefinePlan P;
+    std::string msg;
+    if (int rc = plan_refine(nperseg, hop, fs, band_lo, band_hi, noise_lo, noise_hi, nullptr, 0, 0, P, msg))
+        return fail(rc, "msd_iq_delta64_chain: " + msg);
+    const bool i8 = dtype == MSD_CI16 && !goertzel && i8_supported(P.G, P.K);
+    if (own) *own = i8 ? i8_chain_own() : P.own;
+    if (combine) *combine = refine_chain_combine(P.G.R);
+    if (reference) *reference = refine_chain_reference(P.G.N);
+    return MSD_OK;
+}
+
 int msd_iq_delta64_dev(msd_ctx *ctx, const void *x, int32_t dtype, int64_t n_samples, int32_t nperseg, int64_t hop,
                        double fs, int32_t band_lo, int32_t band_hi, int32_t noise_lo, int32_t noise_hi,
                        const int64_t *ranges, int64_t nranges, double *delta, double *ed) {

@@ -322,6 +322,12 @@ int launch_refine_i8(msd_ctx *ctx, const int16_t *x, const RefineGeom &G, const 
         constexpr int KV = 2 * I8_SUB;
         std::vector<int8_t> Bm((size_t)NT * KV * 16, 0);
         std::vector<int> init((size_t)NT * 16, 0);
+        // T^c, T^s of every needed bin over a sub-block (refine_i8_coeffs: what msd_i8_coeffs kind 2 returns)
+        std::vector<int64_t> Tc((size_t)nk * I8_SUB), Ts((size_t)nk * I8_SUB);
+        for (int b = 0; b < nk; ++b) {
+            refine_i8_coeffs(I8_SUB, N, K.km[b], 0, &Tc[(size_t)b * I8_SUB]);
+            refine_i8_coeffs(I8_SUB, N, K.km[b], 1, &Ts[(size_t)b * I8_SUB]);
+        }
         for (int t = 0; t < NT; ++t)
             for (int cc = 0; cc < 16; ++cc) {
                 if (sumcol(t, cc)) {
@@ -331,17 +337,15 @@ int launch_refine_i8(msd_ctx *ctx, const int16_t *x, const RefineGeom &G, const 
                 }
                 int bin, part, dig;
                 if (!colmap(t, cc, bin, part, dig)) continue;
-                const int64_t km = K.km[bin];
+                const int64_t *tc = &Tc[(size_t)bin * I8_SUB], *ts = &Ts[(size_t)bin * I8_SUB];
                 for (int v = 0; v < KV; ++v) {
-                    const int64_t m = v >> 1;
-                    long double C, S;  // cos, sin of 2 pi km m / N (reduced, long double)
-                    unit_root_ld(km * m, N, C, S);
+                    const int m = v >> 1;
                     // W^{km} = C - i S;  Y = sum (I + i Q)(C - i S): re = I C + Q S, im = Q C - I S
-                    const long double val = part == 0 ? ((v & 1) ? S : C) : ((v & 1) ? C : -S);
+                    // (T = round(w 2^46) from the long-double value: |T 2^-46 - w| <= 2^-47 (1 + 2^-16);
+                    // |T| <= 2^46 fits the six digits; rounding is odd, so -T^s = round(-S 2^46))
+                    const int64_t T = part == 0 ? ((v & 1) ? ts[m] : tc[m]) : ((v & 1) ? tc[m] : -ts[m]);
                     int8_t d[I8_ND];
-                    // T = round(val 2^46) from the long-double value: |T 2^-46 - w| <= 2^-47 (1 + 2^-16);
-                    // |T| <= 2^46 fits the six digits
-                    if (!balanced_digits((int64_t)llroundl(ldexpl(val, 46)), d))
+                    if (!balanced_digits(T, d))
                         return fail(MSD_ERR_INVALID, "refine_i8: twiddle beyond 6 digits");
                     Bm[((size_t)t * KV + v) * 16 + cc] = d[dig];
                     init[t * 16 + cc] += 128 * (int)d[dig];
@@ -417,6 +421,6 @@ int launch_refine_i8(msd_ctx *ctx, const int16_t *x, const RefineGeom &G, const 
 // unit root whose argument was reduced exactly, unit_root_ld), the digit Horner sum (6), the 4 sub-block
 // products summed with rounded twiddles in one 8-FMA chain (10; the budget kept at 22, the
 // 16-sub-block layout's figure)
-double i8_chain_own() { return 91.0 + 6.0 + 22.0; }
+double i8_chain_own() { return MSD_REFINE_I8_CHAIN_QUANT + MSD_REFINE_I8_CHAIN_HORNER + MSD_REFINE_I8_CHAIN_SUBBLOCK; }
 
 }  // namespace msd

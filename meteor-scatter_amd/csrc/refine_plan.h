@@ -44,7 +44,13 @@ struct RefinePlan {
     std::vector<int64_t> fstart, fcs, bstart, bcs;  // per range: first frame, compact frame start;
                                                     // first block, compact block start (+ totals)
     int64_t nblocks = 0, nframes = 0;
+    double own = 0.0;  // the float64 block step's part of G.chain (G.chain = own + G.chain_tail)
 };
+
+// the frame step's part of the chain: the R-block combination (R + 4), the mean, Hann taps and |Y|^2 (8)
+inline double refine_chain_combine(int R) { return (R + 4.0) + 8.0; }
+// the reference's part: pocketfft's chain plus detrend and window
+inline double refine_chain_reference(int N) { return 4.0 * std::log2((double)N) + 11.0; }
 
 // 0, or -1 (bad arguments) / -3 (unsupported) with msg set
 inline int plan_refine(int nperseg, int64_t hop, double fs, int band_lo, int band_hi, int noise_lo, int noise_hi,
@@ -142,8 +148,9 @@ inline int plan_refine(int nperseg, int64_t hop, double fs, int band_lo, int ban
     }
     // the one-lane path sums D direct products (D + 4); the Goertzel path 3 L Gmax + 8 and the 16-lane sum
     const double own = G.rows ? 3.0 * G.L * gmax + 8.0 + 4.0 : (double)G.D + 4.0;
-    G.chain_tail = (G.R + 4.0) + 8.0 + 4.0 * std::log2((double)N) + 11.0;
+    G.chain_tail = refine_chain_combine(G.R) + 4.0 * std::log2((double)N) + 11.0;
     G.chain = own + G.chain_tail;
+    P.own = own;
     if (nranges > (1 << 20)) return err(E_UNSUPPORTED, "too many ranges");
     // frame ranges -> block ranges, compact prefix counts
     std::vector<int64_t> &fstart = P.fstart, &fcs = P.fcs, &bstart = P.bstart, &bcs = P.bcs;

@@ -302,6 +302,9 @@ _SIGS = [
       _P, C.c_int64, _P, _P, _P]),
     ("msd_iq_delta64_path", C.c_int,
      [C.c_int32, C.c_int64, C.c_double, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32]),
+    ("msd_iq_delta64_chain", C.c_int,
+     [C.c_int32, C.c_int64, C.c_double, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32,
+      C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_double)]),
     ("msd_stream_plan_create", C.c_int,
      [_P, C.POINTER(MsdDetCfg), C.c_int64, C.c_int64, C.c_int64, C.c_int64, C.c_int64, C.c_int64, C.POINTER(_P)]),
     ("msd_stream_plan_destroy", None, [_P]),
@@ -764,12 +767,19 @@ class DdcPlan:
                                             out_len.ptr))
 
 
-I8_BLOCK, I8_WELCH = 0, 1
+I8_BLOCK, I8_WELCH, I8_REFINE = 0, 1, 2
 
 
-def i8_coeffs(kind: int, window: np.ndarray, nfft: int, k: int, part: int) -> np.ndarray:
+def i8_coeffs(kind: int, window, nfft: int, k: int, part: int) -> np.ndarray:
     """msd_i8_coeffs: the int64 coefficients T_n of bin k's real (part 0) or imaginary (part 1)
-    component in the block (I8_BLOCK) or Welch (I8_WELCH) int8-MFMA plan (host only)"""
+    component in the block (I8_BLOCK) or Welch (I8_WELCH) int8-MFMA plan, or (I8_REFINE; window: the
+    count L <= 1024 of values wanted, or an array of that length; 0 <= k < nfft) the refinement step's
+    round(cos / sin(2 pi k n / nfft) 2^46) (host only)"""
+    if kind == I8_REFINE:
+        L = int(window) if np.ndim(window) == 0 else len(window)
+        T = np.empty(max(L, 0), np.int64)
+        check(load().msd_i8_coeffs(int(kind), None, L, int(nfft), int(k), int(part), ptr(T)))
+        return T
     w = np.ascontiguousarray(window, dtype=np.float64)
     T = np.empty(w.shape[0], np.int64)
     check(load().msd_i8_coeffs(int(kind), ptr(w), int(w.shape[0]), int(nfft), int(k), int(part), ptr(T)))
@@ -1050,6 +1060,22 @@ def iq_delta64_path(nperseg: int, hop: int, fs: float, band: tuple[int, int], no
                                     int(noise[1]), int(dtype_code_iq))
     check(min(rc, 0))
     return rc
+
+
+# the int8 step's own chain in its parts (include/msdsp.h): twiddle quantisation, digit Horner, sub-block sum
+REFINE_I8_CHAIN_QUANT, REFINE_I8_CHAIN_HORNER, REFINE_I8_CHAIN_SUBBLOCK = 91.0, 6.0, 22.0
+
+
+def iq_delta64_chain(nperseg: int, hop: int, fs: float, band: tuple[int, int], noise: tuple[int, int],
+                     dtype_code_iq: int, goertzel: bool = False) -> tuple[float, float, float]:
+    """msd_iq_delta64_chain: (own, combine, reference), the three parts of the rounding chain behind
+    msd_iq_delta64_dev's ed for the geometry, in units of 2^-53 (host only; goertzel: as a context
+    with OPT_REFINE_GOERTZEL set runs int16 input)"""
+    o, c, r = C.c_double(0.0), C.c_double(0.0), C.c_double(0.0)
+    check(load().msd_iq_delta64_chain(int(nperseg), int(hop), float(fs), int(band[0]), int(band[1]), int(noise[0]),
+                                      int(noise[1]), int(dtype_code_iq), int(bool(goertzel)), C.byref(o), C.byref(c),
+                                      C.byref(r)))
+    return o.value, c.value, r.value
 
 
 def iq_delta64_dev(ctx: Context, x, dtype_code_iq: int, n_samples: int, nperseg: int, hop: int, fs: float,

@@ -118,7 +118,7 @@ def test_welch_coefficients_near_numpy_sum_to_zero_and_fit(L, nfft):
 
 def test_coefficient_entry_refuses_bad_arguments():
     w = dsp.hann_periodic(64)
-    for bad in (lambda: _lib.i8_coeffs(2, w, 64, 0, 0), lambda: _lib.i8_coeffs(0, w, 64, 33, 0),
+    for bad in (lambda: _lib.i8_coeffs(3, w, 64, 0, 0), lambda: _lib.i8_coeffs(0, w, 64, 33, 0),
                 lambda: _lib.i8_coeffs(1, w, 64, 0, 2), lambda: _lib.i8_coeffs(0, 1.5 * w, 64, 0, 0)):
         with pytest.raises(_lib.MsdError) as e:
             bad()

@@ -297,7 +297,8 @@ def test_i8_digits_under_sanitizers(harness, seed):
     # i8_digits.h, the host half of the three int8-MFMA kernels' exactness argument: balanced_digits<6>
     # and <7> reproduce T or refuse it exactly when it does not fit, zero_sum_round's integers sum to 0
     # within 1 of the scaled coefficients, block_i8_coeffs / welch_i8_coeffs (what the plans and
-    # msd_i8_coeffs compute) fit seven digits and sum to zero, frag_sample maps a K step's fragment
-    # bytes onto its samples
+    # msd_i8_coeffs compute) fit seven digits and sum to zero, refine_i8_coeffs (the refinement step's
+    # twiddle integers) fit six digits and 2^46 at N 1024 .. 8192, edge and random bins, with cos = 2^46 at
+    # n = 0, frag_sample maps a K step's fragment bytes onto its samples
     out = run(harness, "i8", seed, 200000)
     assert out.startswith("ok") and out.split()[3] == "200000", out
