@@ -124,7 +124,8 @@ int msd_set_option(msd_ctx *ctx, int option, int value);
  * 4 = Welch band powers, 5 = live detector, 6 = complex (I/Q) STFT, 7 = I/Q band delta,
  * 8 = stream fresh thresholds, 9 = stream scan, 10 = float64 delta (msd_iq_delta64_dev),
  * 11 = the I/Q STFT's post-FFT detrend of bins 0, +-1 (its separate fix-up kernels),
- * 12 = Welch spectrum (msd_welch_spectrum*), 13 = DDC (the down-converter's tile kernel, msd_ddc_*). */
+ * 12 = Welch spectrum (msd_welch_spectrum*), 13 = DDC (the down-converter's tile kernel, msd_ddc_*),
+ * 14 = resampler (the rational resampler's tile kernel, msd_resamp_*). */
 int msd_timing_enable(msd_ctx *ctx, int enable);
 /* which kernels get events while timing is on: bit k = kernel id k (default all); a timed
  * region that times only its roofline kernel carries no events around the others */
@@ -773,6 +774,77 @@ int msd_ddc_push(msd_ddc_plan *plan, int64_t stream, const void *x, int dtype, i
 /* one stream, host buffers: at most ceil(c / D) + 1 outputs */
 int msd_ddc_flush(msd_ddc_plan *plan, int64_t stream, void *y, int64_t cap, int64_t *out_len);
 int msd_ddc_reset(msd_ddc_plan *plan, int64_t stream, int64_t pos0);
+
+/* ------------------------------ rational-ratio resampler: the down-converter at any ratio up / down
+ * The down-converter above decimates by an integer.  This one resamples by L / M = up / down (a polyphase
+ * filter), so that the detector's 4 kHz audio also comes from 6 kHz archive files (2/3), 44.1 kHz sound
+ * cards (40/441) and 250 kHz I/Q (2/125), with the same modes, dtypes, streams and guarantees.
+ *
+ * Contract.  L = up, M = down, gcd(L, M) = 1; h[0 .. ntaps-1]: real float64 taps, ntaps odd, c = (ntaps-1)/2.
+ * Samples outside what a call or a stream has seen count as zero.  Output m:
+ *   t = m M + c,  phi = t mod L,  n0 = t div L,
+ *   v[m] = sum_{i=0}^{I_phi - 1} h[phi + i L] z[n0 - i],  I_phi = ceil((ntaps - phi) / L); a branch with no tap
+ *   (phi >= ntaps) gives exactly 0;
+ *   z = x (mode MSD_DDC_REAL) or x[n] e^{-2 pi i r(n)/q}, r(n) = (n p) mod q exactly in integers (MSD_DDC_SSB),
+ *   p/q = shift_num/shift_den in lowest terms, cycles per input sample;
+ *   y[m] = gain v[m] (REAL) or gain Re(i^m v[m]) (SSB).
+ * In float64 this is scipy.signal.upfirdn(h, x, L, M) read at lag c; REAL at pos0 = 0 is
+ * scipy.signal.resample_poly(x, L, M, window=h/L).  With up = 1 the definition is msd_ddc's (the bits need
+ * not be).
+ * Outputs.  A batch row holding samples [pos0, pos0+N) emits every m with pos0 L <= m M < (pos0+N) L:
+ * ceil((pos0+N) L / M) - ceil(pos0 L / M) of them.  A stream that has received N_tot samples has emitted every
+ * m with m M + c < N_tot L; msd_resamp_flush emits the rest, m M < N_tot L, with zeros for the samples to come
+ * (at most ceil(c / M) + 1 outputs); a flushed stream refuses pushes until it is reset.
+ * msd_resamp_reset(plan, stream, pos0) clears the history and sets the position (stream -1: all).
+ * Per-stream state on the device: the position and the last ceil(ntaps / L) - 1 raw (unmixed) samples, which
+ * suffice because the oldest input of an output not yet emitted is >= N_tot - ceil(ntaps / L) + 1.
+ * Output dtype: MSD_F64, or MSD_I16 = rint(y) (ties to even) saturated to [-32768, 32767].
+ * Arithmetic: float64, no contraction but the kernel's explicit FMAs.  The summation order of an output is a
+ * function of (ntaps, L, M) and the output's branch phi alone (csrc/resamp_plan.h), never of tile, grid,
+ * chunking or entry point: pushes of any lengths followed by flush equal one msd_resamp_run over the
+ * concatenation bit for bit, a row with enough halo (ceil(ntaps / L) samples on each side) equals the whole
+ * stream on its interior outputs bit for bit, and streams pushed together equal each alone.
+ * Non-finite MSD_F32 / MSD_CF32 samples: an output is the IEEE-754 value of its own sum and of nothing else
+ * (no padded tap or sample of another output's window takes part): an output whose window
+ * n0 - I_phi + 1 .. n0 holds no such sample is what it is with that sample replaced by 0, one whose window
+ * holds one is not finite (REAL: +-inf where every infinite product has one sign, NaN otherwise, e.g. where
+ * the tap that meets it is 0), and a branch with no tap still gives 0.  As int16, NaN becomes 0.
+ * Error: |y - y_exact| <= chain u |gain| S_m, u = 2^-53, S_m = sum_i |h[phi + i L]| |x[n0 - i]|, chain =
+ * msd_resamp_chain (counted from the kernel's code, csrc/resamp_plan.h); chain <= 10 + ceil(ntaps / L) + G - 1
+ * with G the plan's partial sums per output.
+ * Limits: 1 <= up <= 256; 1 <= down <= 1024; ntaps odd in 1 .. 4095; q, p and the dtypes as for msd_ddc;
+ * (pos0 + n) up <= 2^62.  gcd(up, down) != 1, an even ntaps, a dtype that does not fit the mode, a bad
+ * out_dtype: MSD_ERR_INVALID; sizes outside the limits or REAL with a shift: MSD_ERR_UNSUPPORTED.
+ * Streams, max_push, the _dev calls' arguments and the host forms' MSD_ERR_CAPACITY are msd_ddc's;
+ * msd_resamp_push_dev needs ld_out >= ceil(max_push L / M) + 1.  Timing id 14. */
+typedef struct {
+    int32_t mode, up, down, ntaps, out_dtype, reserved;
+    int64_t shift_num, shift_den;
+    double gain;
+} msd_resamp_cfg;
+typedef struct msd_resamp_plan msd_resamp_plan;
+int msd_resamp_plan_create(msd_ctx *ctx, const msd_resamp_cfg *cfg, const double *taps, int64_t nstreams,
+                           int64_t max_push, msd_resamp_plan **out);
+void msd_resamp_plan_destroy(msd_resamp_plan *plan);
+/* host only, no context: the first output index and the output count of a row [pos0, pos0 + n) */
+int msd_resamp_out_len(const msd_resamp_cfg *cfg, int64_t pos0, int64_t n, int64_t *m0, int64_t *count);
+/* host only, no context: the rounding chain of the bound above */
+int msd_resamp_chain(const msd_resamp_cfg *cfg, double *chain);
+/* independent rows: row r holds samples [pos0[r], pos0[r] + len[r]) at x[off[r] ..] */
+int msd_resamp_run_dev(msd_resamp_plan *plan, const void *x, int dtype, const int64_t *off, const int64_t *len,
+                       const int64_t *pos0, int64_t nrows, void *y, int64_t ld_out, int64_t *out_len);
+/* one row, host buffers */
+int msd_resamp_run(msd_resamp_plan *plan, const void *x, int dtype, int64_t n, int64_t pos0, void *y, int64_t cap,
+                   int64_t *out_len);
+/* all nstreams: stream f's new samples are x[off[f] .. off[f] + min(len[f], max_push)) */
+int msd_resamp_push_dev(msd_resamp_plan *plan, const void *x, int dtype, const int64_t *off, const int64_t *len,
+                        void *y, int64_t ld_out, int64_t *out_len);
+/* one stream, host buffers, n <= max_push */
+int msd_resamp_push(msd_resamp_plan *plan, int64_t stream, const void *x, int dtype, int64_t n, void *y, int64_t cap,
+                    int64_t *out_len);
+/* one stream, host buffers: at most ceil(c / M) + 1 outputs */
+int msd_resamp_flush(msd_resamp_plan *plan, int64_t stream, void *y, int64_t cap, int64_t *out_len);
+int msd_resamp_reset(msd_resamp_plan *plan, int64_t stream, int64_t pos0);
 
 /* ------------------------------------------- a1 / §8(f)1: WAV ingest and uploads
  * scipy.io.wavfile.read semantics for the reference's files (dsp/src/main.py:249; the rules in

@@ -39,6 +39,7 @@ K_IQDELTA, K_FRESH, K_SSCAN, K_REFINE, K_CSTFT_DC = 7, 8, 9, 10, 11
 K_WSPEC = 12  # Welch spectrum (whole-band rows)
 K_DDC = 13    # the decimating down-converter
 DDC_REAL, DDC_SSB = 0, 1
+K_RESAMP = 14  # the rational-ratio resampler
 OPT_GENERIC_STFT = 1
 OPT_FRESH_ALL = 2
 OPT_REFINE_GOERTZEL = 3
@@ -117,6 +118,21 @@ class MsdDdcCfg(C.Structure):
         ("decim", C.c_int32),
         ("ntaps", C.c_int32),
         ("out_dtype", C.c_int32),
+        ("shift_num", C.c_int64),
+        ("shift_den", C.c_int64),
+        ("gain", C.c_double),
+    ]
+
+
+class MsdResampCfg(C.Structure):
+    """msd_resamp_cfg: the rational-ratio resampler's plan (include/msdsp.h); mode: DDC_REAL or DDC_SSB"""
+    _fields_ = [
+        ("mode", C.c_int32),
+        ("up", C.c_int32),
+        ("down", C.c_int32),
+        ("ntaps", C.c_int32),
+        ("out_dtype", C.c_int32),
+        ("reserved", C.c_int32),
         ("shift_num", C.c_int64),
         ("shift_den", C.c_int64),
         ("gain", C.c_double),
@@ -254,6 +270,17 @@ _SIGS = [
     ("msd_ddc_push", C.c_int, [_P, C.c_int64, _P, C.c_int, C.c_int64, _P, C.c_int64, C.POINTER(C.c_int64)]),
     ("msd_ddc_flush", C.c_int, [_P, C.c_int64, _P, C.c_int64, C.POINTER(C.c_int64)]),
     ("msd_ddc_reset", C.c_int, [_P, C.c_int64, C.c_int64]),
+    ("msd_resamp_plan_create", C.c_int, [_P, C.POINTER(MsdResampCfg), _P, C.c_int64, C.c_int64, C.POINTER(_P)]),
+    ("msd_resamp_plan_destroy", None, [_P]),
+    ("msd_resamp_out_len", C.c_int,
+     [C.POINTER(MsdResampCfg), C.c_int64, C.c_int64, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
+    ("msd_resamp_chain", C.c_int, [C.POINTER(MsdResampCfg), C.POINTER(C.c_double)]),
+    ("msd_resamp_run_dev", C.c_int, [_P, _P, C.c_int, _P, _P, _P, C.c_int64, _P, C.c_int64, _P]),
+    ("msd_resamp_run", C.c_int, [_P, _P, C.c_int, C.c_int64, C.c_int64, _P, C.c_int64, C.POINTER(C.c_int64)]),
+    ("msd_resamp_push_dev", C.c_int, [_P, _P, C.c_int, _P, _P, _P, C.c_int64, _P]),
+    ("msd_resamp_push", C.c_int, [_P, C.c_int64, _P, C.c_int, C.c_int64, _P, C.c_int64, C.POINTER(C.c_int64)]),
+    ("msd_resamp_flush", C.c_int, [_P, C.c_int64, _P, C.c_int64, C.POINTER(C.c_int64)]),
+    ("msd_resamp_reset", C.c_int, [_P, C.c_int64, C.c_int64]),
     ("msd_i8_coeffs", C.c_int, [C.c_int, _P, C.c_int, C.c_int, C.c_int, C.c_int, _P]),
     ("msd_live_detect_dev", C.c_int,
      [_P, _P, _P, C.c_int64, C.c_int64, C.POINTER(MsdLiveCfg), _P, C.c_int64, _P, _P, _P, _P]),
@@ -765,6 +792,88 @@ class DdcPlan:
                  ld_out: int, out_len: DeviceBuffer):
         check(self.ctx.lib.msd_ddc_push_dev(self.h, x.ptr, int(code), off.ptr, length.ptr, y.ptr, int(ld_out),
                                             out_len.ptr))
+
+
+def resamp_out_len(cfg: MsdResampCfg, pos0: int, n: int) -> tuple[int, int]:
+    """msd_resamp_out_len: (first output index, output count) of a row holding samples [pos0, pos0 + n)
+    (host only)"""
+    m0, cnt = C.c_int64(0), C.c_int64(0)
+    check(load().msd_resamp_out_len(C.byref(cfg), int(pos0), int(n), C.byref(m0), C.byref(cnt)))
+    return m0.value, cnt.value
+
+
+def resamp_chain(cfg: MsdResampCfg) -> float:
+    """msd_resamp_chain: the rounding chain of the resampler's error bound (host only)"""
+    v = C.c_double(0.0)
+    check(load().msd_resamp_chain(C.byref(cfg), C.byref(v)))
+    return v.value
+
+
+class ResampPlan:
+    """msd_resamp_plan: the rational-ratio resampler (include/msdsp.h): batch rows and ``nstreams`` streams
+    whose history stays on the device.  Samples as for ``DdcPlan``."""
+
+    def __init__(self, ctx: Context, cfg: MsdResampCfg, taps: np.ndarray, nstreams: int = 1, max_push: int = 1 << 22):
+        self.ctx = ctx
+        t = np.ascontiguousarray(taps, dtype=np.float64)
+        if t.shape != (cfg.ntaps,):
+            raise ValueError("taps length must equal ntaps")
+        h = C.c_void_p()
+        check(ctx.lib.msd_resamp_plan_create(ctx.h, C.byref(cfg), ptr(t), int(nstreams), int(max_push), C.byref(h)))
+        self.h = h
+        self.cfg, self.taps = cfg, t
+        self.nstreams, self.max_push = int(nstreams), int(max_push)
+        self.out_dtype = np.dtype(np.int16 if cfg.out_dtype == MSD_I16 else np.float64)
+        self.c = (int(cfg.ntaps) - 1) // 2
+        self.up, self.down = int(cfg.up), int(cfg.down)
+
+    def close(self):
+        if getattr(self, "h", None) and self.ctx.h:  # a plan outliving its context leaks, never crashes
+            self.ctx.lib.msd_resamp_plan_destroy(self.h)
+            self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def run(self, x: np.ndarray, code: int, n: int, pos0: int = 0) -> np.ndarray:
+        """one row of n samples starting at global index pos0 (host buffers)"""
+        x = np.ascontiguousarray(x)
+        _, cnt = resamp_out_len(self.cfg, pos0, n)
+        y = np.empty(cnt, self.out_dtype)
+        got = C.c_int64(0)
+        check(self.ctx.lib.msd_resamp_run(self.h, ptr(x), int(code), int(n), int(pos0), ptr(y), cnt, C.byref(got)))
+        return y[: got.value]
+
+    def push(self, stream: int, x: np.ndarray, code: int, n: int) -> np.ndarray:
+        x = np.ascontiguousarray(x)
+        cap = -(-n * self.up // self.down) + 1
+        y = np.empty(cap, self.out_dtype)
+        got = C.c_int64(0)
+        check(self.ctx.lib.msd_resamp_push(self.h, int(stream), ptr(x), int(code), int(n), ptr(y), cap, C.byref(got)))
+        return y[: got.value].copy()
+
+    def flush(self, stream: int = 0) -> np.ndarray:
+        cap = self.c // self.down + 2
+        y = np.empty(cap, self.out_dtype)
+        got = C.c_int64(0)
+        check(self.ctx.lib.msd_resamp_flush(self.h, int(stream), ptr(y), cap, C.byref(got)))
+        return y[: got.value].copy()
+
+    def reset(self, stream: int = -1, pos0: int = 0):
+        check(self.ctx.lib.msd_resamp_reset(self.h, int(stream), int(pos0)))
+
+    def run_dev(self, x: DeviceBuffer, code: int, off: DeviceBuffer, length: DeviceBuffer, pos0: DeviceBuffer,
+                nrows: int, y: DeviceBuffer, ld_out: int, out_len: DeviceBuffer):
+        check(self.ctx.lib.msd_resamp_run_dev(self.h, x.ptr, int(code), off.ptr, length.ptr, pos0.ptr, int(nrows),
+                                              y.ptr, int(ld_out), out_len.ptr))
+
+    def push_dev(self, x: DeviceBuffer, code: int, off: DeviceBuffer, length: DeviceBuffer, y: DeviceBuffer,
+                 ld_out: int, out_len: DeviceBuffer):
+        check(self.ctx.lib.msd_resamp_push_dev(self.h, x.ptr, int(code), off.ptr, length.ptr, y.ptr, int(ld_out),
+                                               out_len.ptr))
 
 
 I8_BLOCK, I8_WELCH, I8_REFINE = 0, 1, 2
