@@ -125,7 +125,8 @@ int msd_set_option(msd_ctx *ctx, int option, int value);
  * 8 = stream fresh thresholds, 9 = stream scan, 10 = float64 delta (msd_iq_delta64_dev),
  * 11 = the I/Q STFT's post-FFT detrend of bins 0, +-1 (its separate fix-up kernels),
  * 12 = Welch spectrum (msd_welch_spectrum*), 13 = DDC (the down-converter's tile kernel, msd_ddc_*),
- * 14 = resampler (the rational resampler's tile kernel, msd_resamp_*). */
+ * 14 = resampler (the rational resampler's tile kernel, msd_resamp_*),
+ * 15 = burst clustering (the point extraction and the DBSCAN kernel, msd_spec_peaks_* / msd_cluster*). */
 int msd_timing_enable(msd_ctx *ctx, int enable);
 /* which kernels get events while timing is on: bit k = kernel id k (default all); a timed
  * region that times only its roofline kernel carries no events around the others */
@@ -494,6 +495,65 @@ int msd_spec_band_sum_dev(msd_ctx *ctx, const float *spec, int64_t nfiles, int32
  * float64) */
 int msd_spec_band_sum_f64_dev(msd_ctx *ctx, const double *spec, int64_t nfiles, int32_t K, int64_t frames,
                               int64_t ld, int32_t lo, int32_t hi, double *out);
+
+/* ------------------------------- a11: time-frequency burst clustering of the legacy spectrogram
+ * meteor_detect_class/detector_and_classification.py:7-91 takes points on the 800-1200 Hz spectrogram image
+ * of a 30 s grab, clusters them with DBSCAN(eps=30, min_samples=5).fit(points).labels_ (:20-21), boxes each
+ * cluster (:44-46) and calls it critical when its extent along the time axis is >= 5 px (:48-50).
+ *
+ * msd_spec_peaks_f64*: the points, in the place of cv2.ORB_create(nfeatures=500).detectAndCompute (:12-16;
+ * ORB on a JPEG is not reproducible, the cells above the colour floor are).  spec: float64 [nimg][K][ld] as
+ * msd_stft_psd_f64_dev writes it (the layout of msd_spec_band_sum_f64_dev).  For image m the candidates are
+ * the cells k_lo <= k <= k_hi, t < frames with spec > thr[m] (thr = 10^(vmin/10) of prime_detection.py:86-91's
+ * vmin, computed by the caller: the non-background pixels of the reference image; NaN is never a candidate,
+ * +inf is).  Cell index c = t nk + (k - k_lo), nk = k_hi - k_lo + 1, frame-major.  More than max_points
+ * candidates: the max_points largest by (value descending, c ascending) stay (-0.0 counts as +0.0).  Points
+ * are emitted in ascending c: xy[(m max_points + i) 2 + {0, 1}] = ((double)t sx, (double)(k - k_lo) sy), one
+ * rounded multiply each; cell[m max_points + i] = c; npts[m] = points emitted; ncand[m] = candidates before
+ * the cut (> max_points: the cap bit).  Entries at i >= npts[m] are not written.  nk frames <= 2^31 - 1.
+ *
+ * msd_cluster*: for points p[0 .. n) in float64 (x, y), n = npts[m] <= cfg->max_points <=
+ * MSD_CLUSTER_MAX_POINTS, at xy[(m max_points + i) 2 + {0, 1}]:
+ *   A[i][j] = (dx dx + dy dy) <= eps eps, i == j included, in float64 in that order without contraction;
+ *   core[i] = popcount(A[i]) >= min_samples (sklearn's rule: the point counts itself);
+ *   clusters = the connected components of the core points under A, numbered 0, 1, ... by each component's
+ *   lowest-index core point; a non-core point with a core neighbour takes the lowest cluster id among its
+ *   core neighbours, otherwise it is noise, -1.  These are sklearn's labels_ exactly.
+ *   labels[m max_points + i] (int32), i < n; boxes (may be NULL) [(m max_points + c) 4 + {0..3}] =
+ *   (x_min, y_min, x_max, y_max) over all members of cluster c, border points included; a cluster is critical
+ *   when (x_max - x_min) >= critical_min_extent.  summary[m]: the counts, and status 0, or
+ *   MSD_CLUSTER_STATUS_NPTS where npts[m] is outside 0 .. max_points: that image is not clustered (nothing
+ *   is clamped), its counts are 0 and its labels and boxes are not written; the other images are unaffected.
+ * Points must be finite.  One workgroup per image; the _dev forms enqueue only, no host loop (the label
+ * propagation's rounds are bounded by n on the device).
+ * eps not finite or < 0, min_samples < 1, k_lo > k_hi, k_hi >= K, a non-finite point (host form):
+ * MSD_ERR_INVALID; max_points outside 1 .. MSD_CLUSTER_MAX_POINTS (host form: n above it too):
+ * MSD_ERR_UNSUPPORTED.  Timing id 15 covers both kernels. */
+#define MSD_CLUSTER_MAX_POINTS 512
+#define MSD_CLUSTER_STATUS_NPTS 1
+typedef struct {
+    double eps;                 /* DBSCAN eps (detector_and_classification.py:7: 30) */
+    double critical_min_extent; /* :50: 5 px */
+    int32_t min_samples;        /* :7: 5 */
+    int32_t max_points;         /* row stride of xy / labels / boxes; ORB's nfeatures (:12: 500) */
+} msd_cluster_cfg;
+typedef struct {
+    int32_t n_clusters, n_critical, n_noncritical, n_noise;
+    int32_t status, n_points; /* n_points: the points clustered (0 on a non-zero status) */
+    int32_t reserved[2];
+} msd_cluster_summary;
+int msd_spec_peaks_f64_dev(msd_ctx *ctx, const double *spec, int64_t nimg, int32_t K, int64_t frames, int64_t ld,
+                           int32_t k_lo, int32_t k_hi, const double *thr, double sx, double sy, int32_t max_points,
+                           double *xy, int32_t *cell, int32_t *npts, int32_t *ncand);
+int msd_cluster_dev(msd_ctx *ctx, const msd_cluster_cfg *cfg, const double *xy, const int32_t *npts, int64_t nimg,
+                    int32_t *labels, double *boxes /* nullable */, msd_cluster_summary *summary);
+/* one image, host buffers: spec dense [K][frames]; xy [max_points][2], cell [max_points] */
+int msd_spec_peaks_f64(msd_ctx *ctx, const double *spec, int32_t K, int64_t frames, int32_t k_lo, int32_t k_hi,
+                       double thr, double sx, double sy, int32_t max_points, double *xy, int32_t *cell,
+                       int32_t *npts, int32_t *ncand);
+/* one image, host buffers: xy [n][2], labels [n], boxes (may be NULL) [n][4] of which n_clusters are written */
+int msd_cluster(msd_ctx *ctx, const msd_cluster_cfg *cfg, const double *xy, int32_t n, int32_t *labels,
+                double *boxes /* nullable */, msd_cluster_summary *summary);
 
 /* ------------------------------------------------ a8: Welch band powers (phase 2)
  * Replaces, per processing block of dsp/src/live/backend/processor.py:177-206 and :349-369:

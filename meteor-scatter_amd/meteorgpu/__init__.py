@@ -6,13 +6,16 @@ Public surface (mirrors the reference's dsp/src/main.py):
     write_audacity_labels, count_per_hour
 Batch / multi-GPU: meteorgpu.batch.BatchPipeline.
 Live detector fed in chunks as the audio arrives: LiveSession (meteorgpu.live).
+Time-frequency burst clustering (DBSCAN, boxes, critical rule): meteorgpu.cluster.
 All numerics run in libmsdsp.so (HIP, gfx950); there is no CPU fallback.
 """
 from .dsp import (OutputDetection, ProcResult, block_powers, count_per_hour, get_detections,
                   get_detections_adaptive, proc_wav_file, process_samples, spectrogram, write_audacity_labels,
                   write_csv)
+from .cluster import cluster_points, dbscan, spec_peaks
 from .live import LiveSession
 
-__all__ = ["LiveSession", "OutputDetection", "ProcResult", "block_powers", "count_per_hour", "get_detections",
-           "get_detections_adaptive", "proc_wav_file", "process_samples", "spectrogram", "write_audacity_labels",
-           "write_csv"]
+__all__ = ["LiveSession", "OutputDetection", "ProcResult", "block_powers", "cluster_points", "count_per_hour", "dbscan",
+           "get_detections",
+           "get_detections_adaptive", "proc_wav_file", "process_samples", "spec_peaks", "spectrogram",
+           "write_audacity_labels", "write_csv"]

@@ -40,6 +40,9 @@ K_WSPEC = 12  # Welch spectrum (whole-band rows)
 K_DDC = 13    # the decimating down-converter
 DDC_REAL, DDC_SSB = 0, 1
 K_RESAMP = 14  # the rational-ratio resampler
+K_CLUSTER = 15  # burst clustering: the point extraction and the DBSCAN kernel
+CLUSTER_MAX_POINTS = 512
+CLUSTER_STATUS_NPTS = 1
 OPT_GENERIC_STFT = 1
 OPT_FRESH_ALL = 2
 OPT_REFINE_GOERTZEL = 3
@@ -137,6 +140,34 @@ class MsdResampCfg(C.Structure):
         ("shift_den", C.c_int64),
         ("gain", C.c_double),
     ]
+
+
+class MsdClusterCfg(C.Structure):
+    """msd_cluster_cfg: DBSCAN and the critical rule (include/msdsp.h)"""
+    _fields_ = [
+        ("eps", C.c_double),
+        ("critical_min_extent", C.c_double),
+        ("min_samples", C.c_int32),
+        ("max_points", C.c_int32),
+    ]
+
+
+class MsdClusterSummary(C.Structure):
+    """msd_cluster_summary: one image's counts and status"""
+    _fields_ = [
+        ("n_clusters", C.c_int32),
+        ("n_critical", C.c_int32),
+        ("n_noncritical", C.c_int32),
+        ("n_noise", C.c_int32),
+        ("status", C.c_int32),
+        ("n_points", C.c_int32),
+        ("reserved", C.c_int32 * 2),
+    ]
+
+
+CLUSTER_SUMMARY_DTYPE = np.dtype([("n_clusters", np.int32), ("n_critical", np.int32), ("n_noncritical", np.int32),
+                                  ("n_noise", np.int32), ("status", np.int32), ("n_points", np.int32),
+                                  ("reserved", np.int32, (2,))])
 
 
 class MsdLiveCfg(C.Structure):
@@ -252,6 +283,15 @@ _SIGS = [
     ("msd_spec_band_sum_dev", C.c_int, [_P, _P, C.c_int64, C.c_int32, C.c_int64, C.c_int64, C.c_int32, C.c_int32, _P]),
     ("msd_spec_band_sum_f64_dev", C.c_int,
      [_P, _P, C.c_int64, C.c_int32, C.c_int64, C.c_int64, C.c_int32, C.c_int32, _P]),
+    ("msd_spec_peaks_f64_dev", C.c_int,
+     [_P, _P, C.c_int64, C.c_int32, C.c_int64, C.c_int64, C.c_int32, C.c_int32, _P, C.c_double, C.c_double, C.c_int32,
+      _P, _P, _P, _P]),
+    ("msd_cluster_dev", C.c_int, [_P, C.POINTER(MsdClusterCfg), _P, _P, C.c_int64, _P, _P, _P]),
+    ("msd_spec_peaks_f64", C.c_int,
+     [_P, _P, C.c_int32, C.c_int64, C.c_int32, C.c_int32, C.c_double, C.c_double, C.c_double, C.c_int32, _P, _P,
+      C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
+    ("msd_cluster", C.c_int,
+     [_P, C.POINTER(MsdClusterCfg), _P, C.c_int32, _P, _P, C.POINTER(MsdClusterSummary)]),
     ("msd_welch_plan_create", C.c_int, [_P, C.POINTER(MsdWelchCfg), _P, C.POINTER(_P)]),
     ("msd_welch_plan_destroy", None, [_P]),
     ("msd_welch_bands_dev", C.c_int, [_P, _P, C.c_int, _P, _P, C.c_int64, C.c_int64, _P, C.c_int64, _P]),

@@ -68,3 +68,20 @@ def synth_iq(seed: int, fs: float, duration_s: float, f0: float, sigma: float = 
     i = np.clip(np.rint(z.real), -32768, 32767).astype(np.int16)
     q = np.clip(np.rint(z.imag), -32768, 32767).astype(np.int16)
     return i, q, pings
+
+
+def synth_tones(seed: int, fs: float, duration_s: float, tones, sigma: float = 600.0, dtype=np.int16):
+    """Gaussian noise plus constant-amplitude tone bursts ``tones`` = [(t_start, duration, f_hz, amplitude)]
+    (rectangular envelope, zero phase at the burst's start): a scene with known places on the spectrogram,
+    e.g. two echoes at different Doppler offsets in the same second."""
+    rng = np.random.default_rng(seed)
+    n = int(round(fs * duration_s))
+    x = rng.standard_normal(n) * sigma
+    for t0, d, f, amp in tones:
+        i0 = int(round(t0 * fs))
+        i1 = min(n, i0 + int(round(d * fs)))
+        if i1 > i0:
+            x[i0:i1] += amp * np.sin(2 * np.pi * f * np.arange(i1 - i0) / fs)
+    if np.dtype(dtype) == np.int16:
+        return np.clip(np.rint(x), -32768, 32767).astype(np.int16)
+    return x.astype(dtype)
