@@ -782,10 +782,12 @@ __global__ __launch_bounds__(256) void fresh_short_kernel(const double *__restri
     for (int64_t j = (int64_t)blockIdx.x * 4 + w; j < jend; j += (int64_t)gridDim.x * 4) {
         const int64_t i = P.frame0 + j;
         if (i < P.F0) continue;
-        const int64_t base = P.n_tail + j - i;  // x index of global frame 0 = n_tail - frame0
-        const double m = wave_np_sum(GArrRef{as_global(x)}, base, i) / (double)i;
-        const double v = wave_np_sum(GSqDevRef{as_global(x), m}, base, i);
-        if (lane == 0) fresh[j] = m + P.k * sqrt(v / (double)i);
+        // delta[max(0, i - W):i]; W = 0 sends every frame here with an empty window: 0/0, NaN as numpy's
+        const int64_t len = i < P.W ? i : P.W;
+        const int64_t base = P.n_tail + j - len;  // x index of global frame 0 = n_tail - frame0
+        const double m = wave_np_sum(GArrRef{as_global(x)}, base, len) / (double)len;
+        const double v = wave_np_sum(GSqDevRef{as_global(x), m}, base, len);
+        if (lane == 0) fresh[j] = m + P.k * sqrt(v / (double)len);
     }
 }
 
@@ -1622,7 +1624,11 @@ int msd_stream_scan(msd_stream_plan *p, double thr0, const msd_stream_state *ent
     P.nseg = p->nseg;
     P.cap = p->cap;
     P.F0 = p->cfg.adaptive ? p->cfg.fixed_init_blocks : p->n_total;  // global mode: thr0 everywhere
-    P.Fa = p->cfg.adaptive ? p->cfg.freeze_after_blocks : 0;
+    // main.py:491-493 freezes until max(i + Fa, max(0, i - Fb)): i + max(Fa, -Fb) for Fa >= 0
+    // (a negative freeze-before reaches past the detection, as detect.hip has it)
+    P.Fa = !p->cfg.adaptive ? 0
+           : p->cfg.freeze_after_blocks > -p->cfg.freeze_before_blocks ? p->cfg.freeze_after_blocks
+                                                                       : -p->cfg.freeze_before_blocks;
     P.thr0 = thr0;
     P.write_thr = p->decide ? 0 : 1;  // decisions only: the thresholds buffer is not an output
     P.terr0 = p->terr0;
