@@ -126,7 +126,8 @@ int msd_set_option(msd_ctx *ctx, int option, int value);
  * 11 = the I/Q STFT's post-FFT detrend of bins 0, +-1 (its separate fix-up kernels),
  * 12 = Welch spectrum (msd_welch_spectrum*), 13 = DDC (the down-converter's tile kernel, msd_ddc_*),
  * 14 = resampler (the rational resampler's tile kernel, msd_resamp_*),
- * 15 = burst clustering (the point extraction and the DBSCAN kernel, msd_spec_peaks_* / msd_cluster*). */
+ * 15 = burst clustering (the point extraction and the DBSCAN kernel, msd_spec_peaks_* / msd_cluster*),
+ * 16 = echo measurement (msd_echo_measure*). */
 int msd_timing_enable(msd_ctx *ctx, int enable);
 /* which kernels get events while timing is on: bit k = kernel id k (default all); a timed
  * region that times only its roofline kernel carries no events around the others */
@@ -554,6 +555,77 @@ int msd_spec_peaks_f64(msd_ctx *ctx, const double *spec, int32_t K, int64_t fram
 /* one image, host buffers: xy [n][2], labels [n], boxes (may be NULL) [n][4] of which n_clusters are written */
 int msd_cluster(msd_ctx *ctx, const msd_cluster_cfg *cfg, const double *xy, int32_t n, int32_t *labels,
                 double *boxes /* nullable */, msd_cluster_summary *summary);
+
+/* ------------------------------- a12: echo measurement from the device-resident spectrogram
+ * One fixed-size record per detection of the batch detector, computed from the one-sided spectrogram that is
+ * already in device memory (the reference stops at (start, stop, mean dB), dsp/src/main.py:30-37; these are the
+ * numbers a classifier of echoes starts from).  The I/Q (two-sided) spectrogram and the live path are not
+ * covered.
+ *
+ * Layouts: spec[f K ld + k ld + t] as msd_stft_psd_dev / msd_stft_psd_f64_dev write it; frames[f] (device
+ * int64) = T of file f, <= ld; dets[f cap + i] and counts[f] as msd_detect_dev writes them; out[f cap + i] is
+ * written for i < min(counts[f], cap) and left alone beyond that.
+ *
+ * The span, in int64.  c(s) = the lowest t >= 0 with t hop + nperseg / 2 >= s (the first frame centred at or
+ * after sample s).  For detection i of file f: a0 = min(T, c(start B)), a1 = min(T, c(stop B)) (the core);
+ * lo = the a1 of detection i - 1 (0 for i = 0), hi = the a0 of detection i + 1 (T for the file's last stored
+ * detection); t0 = max(a0 - pre, min(lo, a0), 0), t1 = min(a1 + post, max(hi, a1), T): the padding never
+ * reaches into a neighbour's core or past the file.  Columns at or past T are never read.
+ *
+ * Per frame t of [t0, t1), in float64, every cell converted from the stored type once, no FMA contraction:
+ *   S_t = sum of rows k_lo .. k_hi in ascending k from 0.0;  N_t the same over n_lo .. n_hi;
+ *   k*_t = the lowest k of [k_lo, k_hi] holding the column's maximum;
+ *   with a, b, c the cells at k* - 1, k*, k* + 1 (they may lie outside the band): den = (a - 2 b) + c,
+ *   delta_t = 0.5 (a - c) / den if den < 0, else 0; delta_t = 0 too when k* is row 0 or row K - 1;
+ *   r_t = (k*_t - k_lo) + delta_t.
+ * Per detection:
+ *   p_peak = max S_t, t_peak the lowest frame attaining it; k_peak, d_peak, n_peak = k*, delta, N at t_peak;
+ *   t_half_first / t_half_last = the lowest / highest frame of the span with S_t >= 0.5 p_peak;
+ *   t_efold = the lowest frame after t_peak with S_t <= p_peak 0.36787944117144233 (one rounded multiply),
+ *   or t1 if there is none;
+ *   e_sig = sum S_t, e_noise = sum N_t, and with u = (double)(t - t0): w_r = sum S_t r_t, w_u = sum S_t u,
+ *   w_uu = sum (S_t u) u, w_ur = sum (S_t u) r_t;
+ *   flags: bit 0 t0 > a0 - pre, bit 1 t1 < a1 + post, bit 2 t_efold == t1, bit 3 t_peak is the first or last
+ *   frame of the span.
+ *   An empty span (t0 == t1): p_peak = n_peak = NaN, d_peak = 0, k_peak = -1, the sums 0, flags = bits 0-1, the
+ *   four frame indices = t0.
+ * The order of the six sums across frames is free (each is within (n + 3) 2^-53 sum|term| of any other order,
+ * n frames); everything else is determined bit for bit.  Cells are expected finite and >= 0: NaN cells are
+ * outside the contract (no fault, but the record is then unspecified).
+ *
+ * One wave per detection, lanes along frames; the grid is sized from nfiles and cap, never from a count read
+ * back, and the _dev forms only enqueue on the context's stream.  Timing id 16.
+ * MSD_ERR_INVALID: null pointers, K < 1, k_lo > k_hi or either outside [0, K), n_lo <= n_hi with either
+ * outside [0, K), hop / nperseg / block_size < 1, negative padding, negative nfiles / cap, ld < frames (host
+ * forms).  MSD_ERR_UNSUPPORTED: a signal or noise band of more than MSD_ECHO_MAX_BAND rows. */
+#define MSD_ECHO_MAX_BAND 256
+typedef struct {
+    int64_t block_size;              /* B: samples per detector block (msd_det start / stop are in blocks) */
+    int32_t nperseg, hop;            /* of the spectrogram: frame t covers samples [t hop, t hop + nperseg) */
+    int32_t k_lo, k_hi;              /* signal band, inclusive rows of the spectrogram */
+    int32_t n_lo, n_hi;              /* noise band, inclusive; n_hi < n_lo: empty (noise sums are 0) */
+    int32_t pre_frames, post_frames; /* padding of the span before / after the detection, >= 0 */
+} msd_echo_cfg;
+typedef struct { /* 128 bytes */
+    int64_t t0, t1; /* the span measured, frames [t0, t1) */
+    int64_t t_peak, t_half_first, t_half_last, t_efold;
+    int32_t k_peak, flags;
+    double p_peak, n_peak, d_peak;
+    double e_sig, e_noise, w_r, w_u, w_uu, w_ur;
+} msd_echo;
+int msd_echo_measure_dev(msd_ctx *ctx, const float *spec, int64_t nfiles, int32_t K, const int64_t *frames,
+                         int64_t ld, const msd_det *dets, int64_t cap, const int64_t *counts,
+                         const msd_echo_cfg *cfg, msd_echo *out);
+/* the same over a float64 spectrogram (msd_stft_psd_f64_dev's output) */
+int msd_echo_measure_f64_dev(msd_ctx *ctx, const double *spec, int64_t nfiles, int32_t K, const int64_t *frames,
+                             int64_t ld, const msd_det *dets, int64_t cap, const int64_t *counts,
+                             const msd_echo_cfg *cfg, msd_echo *out);
+/* one file, host buffers: spec [K][ld] of which `frames` columns are valid (dense: ld = frames), the n
+ * detections dets[0 .. n) and out[0 .. n) */
+int msd_echo_measure(msd_ctx *ctx, const float *spec, int32_t K, int64_t frames, int64_t ld, const msd_det *dets,
+                     int64_t n, const msd_echo_cfg *cfg, msd_echo *out);
+int msd_echo_measure_f64(msd_ctx *ctx, const double *spec, int32_t K, int64_t frames, int64_t ld,
+                         const msd_det *dets, int64_t n, const msd_echo_cfg *cfg, msd_echo *out);
 
 /* ------------------------------------------------ a8: Welch band powers (phase 2)
  * Replaces, per processing block of dsp/src/live/backend/processor.py:177-206 and :349-369:

@@ -7,6 +7,8 @@ Public surface (mirrors the reference's dsp/src/main.py):
 Batch / multi-GPU: meteorgpu.batch.BatchPipeline.
 Live detector fed in chunks as the audio arrives: LiveSession (meteorgpu.live).
 Time-frequency burst clustering (DBSCAN, boxes, critical rule): meteorgpu.cluster.
+Echo measurements per batch detection, from the device-resident spectrogram: meteorgpu.echo,
+dsp.measure_detections, BatchPipeline(with_echoes=True).
 All numerics run in libmsdsp.so (HIP, gfx950); there is no CPU fallback.
 """
 from .dsp import (OutputDetection, ProcResult, block_powers, count_per_hour, get_detections,

@@ -41,6 +41,8 @@ K_DDC = 13    # the decimating down-converter
 DDC_REAL, DDC_SSB = 0, 1
 K_RESAMP = 14  # the rational-ratio resampler
 K_CLUSTER = 15  # burst clustering: the point extraction and the DBSCAN kernel
+K_ECHO = 16     # echo measurement from the device-resident spectrogram
+ECHO_MAX_BAND = 256
 CLUSTER_MAX_POINTS = 512
 CLUSTER_STATUS_NPTS = 1
 OPT_GENERIC_STFT = 1
@@ -170,6 +172,29 @@ CLUSTER_SUMMARY_DTYPE = np.dtype([("n_clusters", np.int32), ("n_critical", np.in
                                   ("reserved", np.int32, (2,))])
 
 
+class MsdEchoCfg(C.Structure):
+    """msd_echo_cfg: the spectrogram's framing, the bands and the span's padding (include/msdsp.h)"""
+    _fields_ = [
+        ("block_size", C.c_int64),
+        ("nperseg", C.c_int32),
+        ("hop", C.c_int32),
+        ("k_lo", C.c_int32),
+        ("k_hi", C.c_int32),
+        ("n_lo", C.c_int32),
+        ("n_hi", C.c_int32),
+        ("pre_frames", C.c_int32),
+        ("post_frames", C.c_int32),
+    ]
+
+
+# msd_echo: one detection's record, 128 bytes
+ECHO_DTYPE = np.dtype([("t0", np.int64), ("t1", np.int64), ("t_peak", np.int64), ("t_half_first", np.int64),
+                       ("t_half_last", np.int64), ("t_efold", np.int64), ("k_peak", np.int32), ("flags", np.int32),
+                       ("p_peak", np.float64), ("n_peak", np.float64), ("d_peak", np.float64),
+                       ("e_sig", np.float64), ("e_noise", np.float64), ("w_r", np.float64), ("w_u", np.float64),
+                       ("w_uu", np.float64), ("w_ur", np.float64)])
+
+
 class MsdLiveCfg(C.Structure):
     _fields_ = [
         ("block_size", C.c_int32),
@@ -292,6 +317,14 @@ _SIGS = [
       C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
     ("msd_cluster", C.c_int,
      [_P, C.POINTER(MsdClusterCfg), _P, C.c_int32, _P, _P, C.POINTER(MsdClusterSummary)]),
+    ("msd_echo_measure_dev", C.c_int,
+     [_P, _P, C.c_int64, C.c_int32, _P, C.c_int64, _P, C.c_int64, _P, C.POINTER(MsdEchoCfg), _P]),
+    ("msd_echo_measure_f64_dev", C.c_int,
+     [_P, _P, C.c_int64, C.c_int32, _P, C.c_int64, _P, C.c_int64, _P, C.POINTER(MsdEchoCfg), _P]),
+    ("msd_echo_measure", C.c_int,
+     [_P, _P, C.c_int32, C.c_int64, C.c_int64, _P, C.c_int64, C.POINTER(MsdEchoCfg), _P]),
+    ("msd_echo_measure_f64", C.c_int,
+     [_P, _P, C.c_int32, C.c_int64, C.c_int64, _P, C.c_int64, C.POINTER(MsdEchoCfg), _P]),
     ("msd_welch_plan_create", C.c_int, [_P, C.POINTER(MsdWelchCfg), _P, C.POINTER(_P)]),
     ("msd_welch_plan_destroy", None, [_P]),
     ("msd_welch_bands_dev", C.c_int, [_P, _P, C.c_int, _P, _P, C.c_int64, C.c_int64, _P, C.c_int64, _P]),

@@ -11,6 +11,7 @@ HBM layout:
     thr    f64    [nfiles][ld_b]             thresholds used per block (adaptive)
     dets   {i64 start, i64 stop, f64 db} [nfiles][cap]
     counts i64 [nfiles], margin f64 [nfiles], status i32 [nfiles], hist i64 [nbuckets]
+    echoes msd_echo (128 B) [nfiles][cap]     with_echoes: one record per stored detection, from spec
 Multi-GPU: each rank owns a contiguous range of files; the per-hour histogram is
 summed across ranks with one RCCL all-reduce (``Communicator``).
 """
@@ -30,7 +31,10 @@ class BatchPipeline:
                  threshold_estimation_window_sec: float = 120, threshold_freeze_before_detection_sec: float = 3,
                  threshold_freeze_after_detection_sec: float = 20, threshold_fixed_init_duration_sec: float = 10,
                  with_spectrogram: bool = True, nbuckets: int = 24, bucket_us: int = 3600 * 10 ** 6,
-                 dtype=np.int16, concurrent: bool = False):
+                 dtype=np.int16, concurrent: bool = False, with_echoes: bool = False, echo_pre_sec: float = 0.1,
+                 echo_post_sec: float = 1.0):
+        if with_echoes and not with_spectrogram:
+            raise ValueError("with_echoes needs with_spectrogram=True: the echoes are measured on the spectrogram")
         self.ctx = ctx
         # concurrent: block_delta -> detect run on a second context's stream beside the STFT
         # (they only share the read-only samples); run() forks from and joins back into ctx.
@@ -98,6 +102,18 @@ class BatchPipeline:
         self.d_start_us.upload(np.zeros(F, dtype=np.int64))
         self.hist = _lib.MsdHistCfg(self.d_start_us.ptr, 0, int(bucket_us), self.nbuckets, 0, float(bs),
                                     self.d_hist.ptr)
+        # --- echo measurement (echo.py): the spectrogram's rows of the two bands, the padding in frames
+        self.with_echoes = bool(with_echoes)
+        self.d_echo = self.d_frames = self.echo_cfg = None
+        if self.with_echoes:
+            from . import echo
+            self.echo_bins = band_bins(nperseg, fs, freq_band), band_bins(nperseg, fs, noise_band)
+            self.echo_cfg = echo.echo_cfg(self.block_size, nperseg, self.hop, *self.echo_bins,
+                                          pre_frames=int(echo_pre_sec * fs / self.hop),
+                                          post_frames=int(echo_post_sec * fs / self.hop))
+            self.d_echo = ctx.alloc(F * self.cap * _lib.ECHO_DTYPE.itemsize)
+            self.d_frames = ctx.alloc(F * 8)
+            self.d_frames.upload(np.full(F, self.T, dtype=np.int64))
 
     # ------------------------------------------------------------------ inputs
     def upload_file(self, i: int, x: np.ndarray):
@@ -133,6 +149,10 @@ class BatchPipeline:
                                       self.d_margin.ptr, self.d_status.ptr, self.hist))
         if self.side is not None:
             self.ctx.wait_for(self.side)  # join: everything after run() on ctx sees the detections
+        if self.with_echoes:  # after the join, on ctx: it reads the spectrogram and the detections
+            from . import echo
+            echo.measure_dev(self.ctx, self.d_spec, np.float32, self.nfiles, self.K, self.d_frames, self.ld_t,
+                             self.d_dets, self.cap, self.d_counts, self.echo_cfg, self.d_echo)
 
     @property
     def contexts(self):
@@ -166,6 +186,16 @@ class BatchPipeline:
         self._near_ties(margin)
         return [dets[i, : min(counts[i], self.cap)] for i in range(self.nfiles)], counts, status, margin
 
+    def echoes(self):
+        """Per file: the echo records (echo.ECHO_DTYPE) of its stored detections, in their order."""
+        if not self.with_echoes:
+            raise RuntimeError("the pipeline was built with with_echoes=False")
+        counts = np.empty(self.nfiles, np.int64)
+        self.d_counts.download(counts)
+        rec = np.empty((self.nfiles, self.cap), _lib.ECHO_DTYPE)
+        self.d_echo.download(rec)
+        return [rec[i, : max(0, min(counts[i], self.cap))] for i in range(self.nfiles)]
+
     def _near_ties(self, margin: np.ndarray):
         """Per file: the decision bound (margin.py) and whether min |delta - thr| is within it
         (``self.decision_bounds``, ``self.near_tie``); one NearTieWarning names the files."""
@@ -196,7 +226,8 @@ class BatchPipeline:
         for pl in (self.stft, self.blocks):
             pl.close()
         for b in (self.d_x, self.d_off, self.d_len, self.d_nb, self.d_spec, self.d_delta, self.d_band, self.d_noise,
-                  self.d_thr, self.d_dets, self.d_counts, self.d_margin, self.d_status, self.d_start_us, self.d_hist):
+                  self.d_thr, self.d_dets, self.d_counts, self.d_margin, self.d_status, self.d_start_us, self.d_hist,
+                  self.d_echo, self.d_frames):
             if b is not None:
                 b.free()
 

@@ -9,6 +9,8 @@ work runs on the GPU through libmsdsp (no CPU fallback).  Lower-level pieces:
 * ``spectrogram``   — scipy.signal.spectrogram as called at main.py:52-54, :132-133
 * ``write_csv`` / ``write_audacity_labels`` — main.py:640-658 / 630-638
 * ``count_per_hour`` — main.py:687-696 (Counter over utc_start hours)
+* ``measure_detections`` — beyond the reference: peak, sub-bin frequency, drift and decay of each detection's
+  echo, measured on the device-resident spectrogram (echo.py); ``out_echo_csv_file`` writes them
 
 The reference's figures are drawn from GPU arrays with matplotlib / plotly (``figures.py``):
 the per-detection spectrogram + PSD export (``disable_show_and_write=False``,
@@ -273,6 +275,109 @@ def spectrogram(x, fs=1.0, window="hann", nperseg=None, noverlap=None, nfft=None
     return freqs, time, sxx
 
 
+# --------------------------------------------------------------------------- echo measurement
+@dataclass
+class EchoResult:
+    """measure_detections' output: the raw records (echo.ECHO_DTYPE), their physical units
+    (echo.PARAM_DTYPE), and the configuration they were measured with."""
+    raw: np.ndarray
+    params: np.ndarray
+    detections: np.ndarray  # the detections in blocks (_lib.DET_DTYPE)
+    block_size: int
+    nperseg: int
+    hop: int
+    frames: int
+    band_bins: tuple
+    noise_bins: tuple
+    pre_frames: int
+    post_frames: int
+    spectrogram: np.ndarray = None  # [K][frames], the buffer that was measured (return_spectrogram=True)
+
+
+def _detection_blocks(detections_or_result, block_duration_sec) -> np.ndarray:
+    d = getattr(detections_or_result, "detections", detections_or_result)
+    if isinstance(d, np.ndarray) and d.dtype == _lib.DET_DTYPE:
+        return np.ascontiguousarray(d)
+    out = np.zeros(len(d), _lib.DET_DTYPE)
+    for i, det in enumerate(d):  # t_start = start * block_duration_sec (get_detections*)
+        out[i] = (int(round(det.t_start / block_duration_sec)), int(round(det.t_stop / block_duration_sec)), det.dB)
+    return out
+
+
+def measure_detections(wav_data, fs, detections_or_result, block_duration_sec, freq_band, noise_band, nperseg=1024,
+                       noverlap=None, pre_sec=0.1, post_sec=1.0, device: int = 0,
+                       return_spectrogram: bool = False) -> EchoResult:
+    """Echo measurements of a file's detections (a ProcResult, a list of OutputDetection, or an array of
+    _lib.DET_DTYPE in blocks): the spectrogram of ``spectrogram(wav_data, fs, nperseg=, noverlap=)`` is computed
+    on the device and measured there, without downloading it.  ``noverlap`` defaults to 7/8 of nperseg (a frame
+    every nperseg / 8 samples: the decay of an echo is a few frames of the reference's 50 % overlap).  The band
+    rows are band_bins(nperseg, fs, band); the span reaches pre_sec before and post_sec after each detection,
+    int(sec * fs / hop) frames, short of its neighbours.  ``return_spectrogram`` also downloads the buffer that
+    was measured (``EchoResult.spectrogram``, [K][frames])."""
+    from . import echo
+    x = np.asarray(wav_data)
+    if x.ndim != 1 or np.iscomplexobj(x):
+        raise NotImplementedError("only real 1-D input is implemented (I/Q: out of scope)")
+    double = np.result_type(x.dtype, np.complex64) == np.complex128  # spectrogram()'s precision rule
+    if x.dtype not in (np.uint8, np.int16, np.int32, np.float32, np.float64):
+        x = x.astype(np.float64)
+    x = np.ascontiguousarray(x)
+    nperseg = int(nperseg)
+    noverlap = nperseg - max(1, nperseg // 8) if noverlap is None else int(noverlap)
+    if not 0 <= noverlap < nperseg:
+        raise ValueError("noverlap must be less than nperseg.")
+    hop = nperseg - noverlap
+    dets = _detection_blocks(detections_or_result, block_duration_sec)
+    bins, nbins = band_bins(nperseg, fs, freq_band), band_bins(nperseg, fs, noise_band)
+    pre, post = int(pre_sec * fs / hop), int(post_sec * fs / hop)
+    block_size = int(fs * block_duration_sec)
+    ctx = context(device)
+    w64 = hann_periodic(nperseg)
+    wc = w64.astype(np.complex128 if double else np.complex64)
+    scale = float(np.real(1.0 / (fs * (wc * wc).sum())))
+    sdt = np.dtype(np.float64 if double else np.float32)
+    plan = _lib.StftPlan(ctx, nperseg, hop, wc.real, scale, precision=sdt)
+    n = x.shape[0]
+    T = plan.frames(n)
+    ld = max(32, (T + 31) // 32 * 32)
+    K, ndet = plan.nbins, dets.shape[0]
+    raw = np.zeros(ndet, echo.ECHO_DTYPE)
+    spec = None
+    bufs = []
+
+    def dev(a):
+        a = np.ascontiguousarray(a)
+        bufs.append(ctx.alloc(max(16, a.nbytes)))
+        if a.nbytes:
+            bufs[-1].upload(a)
+        return bufs[-1]
+    try:
+        if ndet:
+            d_x = ctx.alloc((x.nbytes + 255) // 256 * 256)  # whole 256-B lines, as the one-file host forms stage it
+            bufs.append(d_x)
+            d_x.upload(x)
+            d_off, d_len = dev(np.zeros(1, np.int64)), dev(np.array([n], np.int64))
+            d_frames, d_counts, d_dets = dev(np.array([T], np.int64)), dev(np.array([ndet], np.int64)), dev(dets)
+            d_spec, d_out = ctx.alloc(K * ld * sdt.itemsize), ctx.alloc(ndet * echo.ECHO_DTYPE.itemsize)
+            bufs += [d_spec, d_out]
+            if T:  # a signal shorter than a frame has no spectrogram: every span is empty, nothing is read
+                plan.run_dev(d_x, x.dtype, d_off, d_len, 1, T, d_spec, ld)
+            cfg = echo.echo_cfg(block_size, nperseg, hop, bins, nbins, pre, post)
+            echo.measure_dev(ctx, d_spec, sdt, 1, K, d_frames, ld, d_dets, ndet, d_counts, cfg, d_out)
+            d_out.download(raw)
+            if return_spectrogram:
+                spec = np.empty((K, ld), sdt)
+                d_spec.download(spec)
+                spec = np.ascontiguousarray(spec[:, :T])
+    finally:
+        ctx.synchronize()
+        plan.close()
+        for b in bufs:
+            b.free()
+    params = echo.parameters(raw, fs, nperseg, hop, nperseg, bins, nbins)
+    return EchoResult(raw, params, dets, block_size, nperseg, hop, T, bins, nbins, pre, post, spec)
+
+
 # --------------------------------------------------------------------------- main.py:207-806
 def proc_wav_file(file_path,
                   block_duration_sec,
@@ -300,12 +405,15 @@ def proc_wav_file(file_path,
                   required_sample_rate=6000,
                   device=0,
                   verbose=True,
-                  figure_dir=None):
+                  figure_dir=None,
+                  out_echo_csv_file=None):
     """GPU drop-in for dsp/src/main.py:207-806 (same arguments, asserts and outputs).
 
     ``required_sample_rate`` keeps the reference's ``assert fs == 6000`` (main.py:267);
     pass ``None`` to accept any rate (e.g. the 48 kHz configurations).  ``figure_dir``: also
-    save every debug figure there (PNG; plotly figures as HTML instead of fig.show())."""
+    save every debug figure there (PNG; plotly figures as HTML instead of fig.show()).
+    ``out_echo_csv_file``: also write the detections with their echo measurements (measure_detections,
+    echo.write_echo_csv) there; the reference's CSV is unchanged."""
     say = print if verbose else (lambda *a, **k: None)
     assert os.path.exists(file_path), f"File does not exist: {file_path}"
     if outfile_path is not None:
@@ -320,6 +428,9 @@ def proc_wav_file(file_path,
     if out_csv_file is not None:
         assert os.path.exists(os.path.dirname(out_csv_file)), \
             f"Output directory does not exist: {os.path.dirname(out_csv_file)}"
+    if out_echo_csv_file is not None:
+        assert os.path.exists(os.path.dirname(out_echo_csv_file)), \
+            f"Output directory does not exist: {os.path.dirname(out_echo_csv_file)}"
     wav_sample_rate, wav_data = wav.read(file_path)
 
     if wav_start_sec is not None or wav_end_sec is not None:
@@ -371,6 +482,12 @@ def proc_wav_file(file_path,
     if out_csv_file is not None:
         write_csv(res.detections, out_csv_file)
         say("Wrote Items", len(res.detections), "to CSV file:", out_csv_file)
+    if out_echo_csv_file is not None:
+        from . import echo
+        ech = measure_detections(wav_data, wav_sample_rate, res, block_duration_sec, freq_band, noise_band,
+                                 device=device)
+        echo.write_echo_csv(res.detections, ech.params, out_echo_csv_file)
+        say("Wrote Items", len(res.detections), "to echo CSV file:", out_echo_csv_file)
     if debug_plot_output:  # main.py:660-716: histograms, then the per-hour map
         figures.debug_output_hists(res.detections, figure_dir)
         figures.debug_time_map(res.detections, figure_dir)
